@@ -6,12 +6,17 @@ in HBM.  The step is captured once in a HIP graph and replayed.  N GPUs = N inde
 replicas (inference does not shard further: "replicas only", weak scaling), launched one
 process per GPU by torch.distributed.run; max-over-ranks time.
 
-Printed JSON adds `roofline` (the dominant kernel family -- the implicit-GEMM engine's
+A plain run sets up, warms up, times the steps and prints one JSON line (`value`,
+`ms_per_step`, and `path_roofline`: the whole G forward's useful FLOPs over the timed step);
+`--dump-outputs DIR` also writes the last timed step's poses to DIR/pose.npy.  Everything that
+takes runs of its own is behind `--full`:
+
+With `--full` the printed JSON adds `roofline` (the dominant kernel family -- the implicit-GEMM engine's
 gemm_kernel, ~65 % of kernel time -- every launch of the replayed step graph timed by its own
 span stamps (first block start to last wave end on the GPU wall clock, the interval rocprof's
 kernel trace reports), algorithmic FLOPs 2*M*N*K per launch, against the fp32 MFMA peak;
 `traffic` from the committed PMC pass, profiles/traffic_latest.json), `mel_roofline`
-(log-mel kernel vs HBM peak), `path_roofline` (the whole G forward's useful FLOPs) and
+(log-mel kernel vs HBM peak), `mel_encoder_roofline` and
 `cpu_baseline` (the torch-CPU oracle port on a bounded sample, rank 0 at N=1 only).
 """
 import argparse
@@ -410,6 +415,26 @@ def cpu_baseline(B=64, T=64, max_s=40.0):
                       f'(affinity {avail} CPUs, cgroup quota {granted or "none"})'}
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(path, arrays):
+    """`--dump-outputs DIR`: what the timed path returned in its last step, one DIR/<name>.npy per
+    array (float64 stays float64, everything else as float32), at most 64 MB in all: an array
+    over its share is cut to a sample of its flattened elements at fixed, seeded indices (the
+    same ones every run), so two builds can be compared output for output."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    share = DUMP_MAX_BYTES // max(len(arrays), 1)
+    for name, t in arrays.items():
+        t = t.detach()
+        a = t.to('cpu', torch.float64 if t.dtype == torch.float64 else torch.float32).numpy()
+        if a.nbytes > share:
+            idx = np.sort(np.random.default_rng(0).integers(0, a.size, share // a.itemsize))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(path, name + '.npy'), a)
+
+
 # SURVEY.md 8(d): dense FLOPs of one training iteration at T=64 measured with torch's
 # FlopCounter on the reference modules: 3 G-steps x 891.7 GF + 1 D-step x 382.8 GF per 64 clips.
 TRAIN_GFLOP_PER_CLIP_T64 = (3 * 891.7 + 382.8) / 64
@@ -434,7 +459,7 @@ def run_train(args, world, rank, dev):
     pose = torch.randn(B, T, 104, generator=gen).to(dev)
 
     def step(epoch):
-        tr.iteration(audio, pose, epoch=epoch, g_freq=3, d_freq=1)
+        return tr.iteration(audio, pose, epoch=epoch, g_freq=3, d_freq=1)
 
     for i in range(args.warmup):
         step(i)
@@ -443,8 +468,9 @@ def run_train(args, world, rank, dev):
         dist.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
+    losses = None
     for i in range(args.steps):
-        step(args.warmup + i)
+        losses = step(args.warmup + i)
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
@@ -454,6 +480,8 @@ def run_train(args, world, rank, dev):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = t.item()
     tr.flush()   # the ranks agree that every step's gradients followed the bucket plan
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {'d_loss': losses[0], 'g_loss': losses[1]})
     ms = elapsed / args.steps * 1e3
     flops = TRAIN_GFLOP_PER_CLIP_T64 * 1e9 * B * T / 64           # per rank
     tf = flops * world / (ms * 1e-3) / 1e12
@@ -678,6 +706,46 @@ def build_infer(B, T, rank, dev):
     return g, synth_wave(B, n, seed=rank, device=dev)
 
 
+def full_measurements(args, world, dev, g, wave, step, run, graph):
+    """`--full`, after the timed steps: the result line's `roofline`, `mel_roofline` and
+    `mel_encoder_roofline` entries, each from runs of its own (span-stamped captures of the
+    step, isolated log-mel / encoder graphs, a kernel trace of a child run)."""
+    from a2m import functional as AF
+    from a2m.mel_features import log_mel_batch
+    B, T = args.batch, args.frames
+    peak = mfma_peak(args.dtype)
+    gt = gemm_engine_timing(step)
+    warm = None if graph is None else (lambda: [run() for _ in range(3)])
+    with AF.gemm_timing() as et:   # the encoder's engine launches come first in the step
+        g.audio_encoder(log_mel_batch(wave))
+    it = instep_timing(dev, g, wave, warm=warm, enc_last=et.launches - 1)
+    it['mel_ms'] = instep_timing(dev, g, wave, warm=warm, marks=(0, 1), gemm=False)['mel_ms']
+    disp_ms = dispatch_overhead_ms(dev)
+    mel_ms, mel_bytes = run_mel_kernel(dev, wave)
+    mel_enc = mel_encoder_roofline(dev, g, wave, mel_ms, mel_bytes, peak)
+    mel_enc['instep_mel_ms'] = round(it['mel_ms'], 4)
+    mel_enc['instep_mel_encoder_ms'] = round(it['mel_enc_ms'], 4)
+    mel_enc['path_frac_instep'] = round(mel_enc['path_roofline_ms'] / it['mel_enc_ms'], 4)
+    tr = None
+    if world == 1 and not args.no_trace and graph is not None and not args.branch_graphs and \
+            not under_profiler():
+        tr = traced_family(args, it['flops'], keep_dir=os.environ.get('A2M_BENCH_TRACE_DIR'))
+    if tr and tr['mel_enc_us']:
+        mel_enc['instep_mel_encoder_ms_trace'] = round(tr['mel_enc_us'] / 1e3, 4)
+        mel_enc['path_frac_instep_trace'] = round(mel_enc['path_roofline_ms'] / (tr['mel_enc_us'] / 1e3), 4)
+    return {
+        'roofline': roofline_entry(it, gt, peak, disp_ms, tr),
+        'mel_roofline': {'bound': 'hbm', 'achieved': round(mel_bytes / (mel_ms * 1e-3) / 1e9, 1),
+                         'peak': HBM_PEAK_GBS, 'unit': 'GB/s',
+                         'frac': round(mel_bytes / (mel_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
+                         'ms_per_launch': round(mel_ms, 4),
+                         'algorithmic_bytes': int(mel_bytes),
+                         'traffic': (load_traffic('logmel2048_kernel') or {}).get('bytes_per_launch')
+                         if (B, T) == (64, 64) else None,
+                         'note': 'VALU-issue bound (DESIGN.md 4): ~732 VALU instructions per frame-wave'},
+        'mel_encoder_roofline': mel_enc,
+    }
+
 
 def spawn_ranks(n):
     """`bench.py --gpus N` without a launcher: start N ranks as fresh child processes of
@@ -706,7 +774,14 @@ def main():
     ap.add_argument('--branch-graphs', action='store_true',
                     help='replay a2m.inference.GraphedGenerator (one graph per decoder branch, '
                          'two streams) instead of one graph with the branches forked inside')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--full', action='store_true',
+                    help='infer mode: after the timed steps also measure the engine / log-mel / '
+                         'mel + encoder rooflines (span stamps, a rocprofv3 kernel trace of a child '
+                         'run) and the torch-CPU baseline, and add them to the result line')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write what the last timed step returned as DIR/<name>.npy (infer: pose; '
+                         'train: d_loss, g_loss)')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the CPU baseline')
     ap.add_argument('--mode', choices=('infer', 'train'), default='infer')
     ap.add_argument('--sync-bn', action='store_true',
                     help='train mode: SyncBN over the DP ranks (SURVEY 8(e)); default per-rank statistics')
@@ -716,7 +791,7 @@ def main():
                     help='GEMM operand precision (bf16: configs[4], fp32 accumulation/storage)')
     ap.add_argument('--trace-child', type=int, default=0, help=argparse.SUPPRESS)
     ap.add_argument('--no-trace', action='store_true',
-                    help='skip the kernel-trace pass (roofline from the span stamps only)')
+                    help='with --full: skip the kernel-trace pass (roofline from the span stamps only)')
     args = ap.parse_args()
     if args.trace_child:
         return trace_child(args)
@@ -776,8 +851,9 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
         t0 = time.perf_counter()
+        last = None
         for _ in range(args.steps):
-            run()
+            last = run()
         torch.cuda.synchronize()
         if world > 1:
             dist.barrier()
@@ -786,32 +862,15 @@ def main():
             t = torch.tensor([elapsed], device=dev, dtype=torch.float64)
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             elapsed = t.item()
-        out = static_out if graph is not None else step()
+        # the last timed step's poses: the replayed graph's static output, or the eager step's result
+        out = static_out if graph is not None else last
         assert torch.isfinite(out).all()
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, {'pose': out})
 
         ms_step = elapsed / args.steps * 1e3
         value = world * B * T / (elapsed / args.steps)
-        gt = gemm_engine_timing(step)
-        warm = None if graph is None else (lambda: [run() for _ in range(3)])
-        from a2m import functional as AF
-        from a2m.mel_features import log_mel_batch
-        with AF.gemm_timing() as et:   # the encoder's engine launches come first in the step
-            g.audio_encoder(log_mel_batch(wave))
-        it = instep_timing(dev, g, wave, warm=warm, enc_last=et.launches - 1)
-        it['mel_ms'] = instep_timing(dev, g, wave, warm=warm, marks=(0, 1), gemm=False)['mel_ms']
-        disp_ms = dispatch_overhead_ms(dev)
-        mel_ms, mel_bytes = run_mel_kernel(dev, wave)
-        mel_enc = mel_encoder_roofline(dev, g, wave, mel_ms, mel_bytes, mfma_peak(args.dtype))
-        mel_enc['instep_mel_ms'] = round(it['mel_ms'], 4)
-        mel_enc['instep_mel_encoder_ms'] = round(it['mel_enc_ms'], 4)
-        mel_enc['path_frac_instep'] = round(mel_enc['path_roofline_ms'] / it['mel_enc_ms'], 4)
-        tr = None
-        if world == 1 and not args.no_trace and graph is not None and not args.branch_graphs and \
-                not under_profiler():
-            tr = traced_family(args, it['flops'], keep_dir=os.environ.get('A2M_BENCH_TRACE_DIR'))
-        if tr and tr['mel_enc_us']:
-            mel_enc['instep_mel_encoder_ms_trace'] = round(tr['mel_enc_us'] / 1e3, 4)
-            mel_enc['path_frac_instep_trace'] = round(mel_enc['path_roofline_ms'] / (tr['mel_enc_us'] / 1e3), 4)
+        extra = full_measurements(args, world, dev, g, wave, step, run, graph) if args.full else {}
     path_tf = g_forward_flops(B, T) / (ms_step * 1e-3) / 1e12
     peak = mfma_peak(args.dtype)
     if args.dtype == 'bf16':
@@ -831,21 +890,12 @@ def main():
         'data': 'synthetic 16 kHz speech-like audio, random-init weights',
         'config': {'workload': workload, 'global_batch': B * world, 'seq_len': T,
                    'parallelism': f'replicas{world}', 'hip_graph': 'none' if graph is None else ('per-branch graphs, two streams' if args.branch_graphs else 'one graph')},
-        'roofline': roofline_entry(it, gt, peak, disp_ms, tr),
-        'mel_roofline': {'bound': 'hbm', 'achieved': round(mel_bytes / (mel_ms * 1e-3) / 1e9, 1),
-                         'peak': HBM_PEAK_GBS, 'unit': 'GB/s',
-                         'frac': round(mel_bytes / (mel_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
-                         'ms_per_launch': round(mel_ms, 4),
-                         'algorithmic_bytes': int(mel_bytes),
-                         'traffic': (load_traffic('logmel2048_kernel') or {}).get('bytes_per_launch')
-                         if (B, T) == (64, 64) else None,
-                         'note': 'VALU-issue bound (DESIGN.md 4): ~732 VALU instructions per frame-wave'},
-        'mel_encoder_roofline': mel_enc,
+        **extra,
         'path_roofline': {'bound': 'mfma', 'achieved': round(path_tf, 2), 'peak': peak,
                           'unit': 'TFLOP/s', 'frac': round(path_tf / peak, 4),
                           'gflop_per_step': round(g_forward_flops(B, T) / 1e9, 1)},
     }
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         result['cpu_baseline'] = cpu_baseline()
     if args.rehearsal:
         result['rehearsal'] = args.rehearsal
