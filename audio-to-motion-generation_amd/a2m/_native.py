@@ -28,6 +28,12 @@ SIGNATURES = {
     'a2m_logmel_plan_bytes': (SZ, [I32, F64, F64, I32, F64, F64]),
     'a2m_logmel_plan_build': (ctypes.c_int, [I32, F64, F64, I32, F64, F64, P, SZ]),
     'a2m_logmel_f32': (ctypes.c_int, [P, I64, I64, I64, I32, I32, I32, I32, P, F32, P, P]),
+    'a2m_pats_audio_plan_bytes': (SZ, [I32, I32, I32, I32, I32, F64, F64, I32, I32]),
+    'a2m_pats_audio_plan_build': (ctypes.c_int, [I32, I32, I32, I32, I32, F64, F64, I32, I32, P, SZ]),
+    'a2m_pats_audio_plan_filterbank': (ctypes.c_int, [P, SZ, P]),
+    'a2m_pats_audio_num_frames': (I64, [I64, I32, I32, I32]),
+    'a2m_pats_audio_f32': (ctypes.c_int, [P, I64, I64, I64, I32, I32, I32, I32, I32, P, I32, I32, F32,
+                                          P, I64, P, P, P, P]),
     'a2m_conv1d_fwd_f32': (ctypes.c_int, [P, I64, I64, I64, I32, I32, I32, P, P, I32, I32, I32, I32,
                                           P, P, P, P, F32, I32, F32, P, I64, I64, I64, P, SZ, P]),
     'a2m_convt1d_fwd_f32': (ctypes.c_int, [P, I64, I64, I32, I32, I32, P, P, I32, I32, I32, I32, I32,

@@ -3,6 +3,8 @@
   load_generator(path)      :237-238  construct + load_state_dict (weights_only) + eval
   generate(g, audio, ...)   :247-260  generator(audio) on normalised audio features, then the
                                       normalised poses mapped back: pose * std + mean
+  generate_from_wave(g, wave, sr, ...)  the same from a raw recording: PATS log_mel_512 windows
+                                      (pats_audio.log_mel_512_windows) -> generate
   planar_frames(pose)       :262-266  [B, T, 104] -> [B, T, 2, 52] (x row, y row) for plotting
 
   GraphedGenerator(g, ...)  HIP-graph replay of a fixed-shape eval forward (the serving loop
@@ -31,6 +33,25 @@ def generate(generator, audio, pose_mean=None, pose_std=None):
     if pose_mean is not None:
         pose = denormalize(pose, pose_mean.to(pose.device), pose_std.to(pose.device))
     return pose
+
+
+@torch.no_grad()
+def generate_from_wave(generator, wave, sr, starts=None, time=4.3, fs_new=15, audio_mean=None,
+                       audio_std=None, pose_mean=None, pose_std=None, **mel_kwargs):
+    """A recording to poses in one call: wave [S] (device) -> audio/log_mel_512 windows as the
+    PATS loader cuts them (windowing.window_index: `time` seconds at 89 feature frames/s read
+    every round(89 / fs_new)-th frame, i.e. 382 / 6 -> T = 64; only those frames are computed),
+    standardised with audio_mean / audio_std when given -> generator -> poses [n, T, 104],
+    de-normalised when pose_mean / pose_std are given.  `starts` (feature-frame index of each
+    window) defaults to the loader's non-overlapping windows; mel_kwargs go to
+    pats_audio.log_mel_512_windows (eps, pad_mode)."""
+    from .pats_audio import log_mel_512_windows, num_frames
+    from .windowing import window_index
+    auto, window, interval = window_index(num_frames(wave.shape[-1], 2048, 512, True),
+                                          'audio/log_mel_512', fs_new, time)
+    audio = log_mel_512_windows(wave, sr, auto if starts is None else starts, window, interval,
+                                audio_mean, audio_std, **mel_kwargs)
+    return generate(generator, audio, pose_mean, pose_std)
 
 
 def planar_frames(pose):

@@ -10,6 +10,12 @@
 //   4. banded mel filterbank (CSR, <= a few dozen taps per band, built on the host in
 //      float64 exactly as spectrogram_to_mel_matrix :114-189 does) and log(mel + offset).
 // HBM traffic per frame: the window (mostly L2 hits for overlapping frames) + n_mels*4 B.
+//
+// The PATS features audio/log_mel_512 and audio/log_mel_400 (pats/data_loading/audio.py:58-120,
+// librosa.feature.melspectrogram) run through the same two kernels (template flag PATS): frames
+// of fft_len samples, centred with reflected or zero edges or uncentred, a window shorter than
+// the frame centred in it, power or magnitude spectrum, Slaney filterbank (slaney_weights), exact
+// zeros replaced by eps before the log, and an optional output -> source frame map.
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
@@ -88,15 +94,109 @@ static int mel_weights(int n_mels, int n_bins, int sr, double lo, double hi,
   return A2M_OK;
 }
 
+// Slaney mel weights in float64, librosa.filters.mel(htk=False): the scale is linear (200/3 Hz per
+// mel) below 1 kHz and logarithmic (27 mels per factor 6.4) above, the triangles are linear in
+// Hz between the n_mels + 2 band edges, and with `norm` each is scaled to unit area,
+// 2 / (upper edge - lower edge).  Stored like mel_weights: w[k * n_mels + m].
+static int slaney_weights(int n_mels, int n_bins, int sr, double lo, double hi, bool norm,
+                          std::vector<double>* w) {
+  const double nyq = sr / 2.0;
+  if (lo < 0.0) { set_error("fmin %.1f must be >= 0", lo); return A2M_EINVAL; }
+  if (lo >= hi) { set_error("fmin %.1f >= fmax %.1f", lo, hi); return A2M_EINVAL; }
+  if (hi > nyq) { set_error("fmax %.1f is greater than Nyquist %.1f", hi, nyq); return A2M_EINVAL; }
+  const double f_sp = 200.0 / 3.0, min_log_hz = 1000.0, min_log_mel = min_log_hz / f_sp;
+  const double logstep = std::log(6.4) / 27.0;
+  auto to_mel = [&](double f) {
+    return f >= min_log_hz ? min_log_mel + std::log(f / min_log_hz) / logstep : f / f_sp;
+  };
+  auto to_hz = [&](double m) {
+    return m >= min_log_mel ? min_log_hz * std::exp(logstep * (m - min_log_mel)) : f_sp * m;
+  };
+  std::vector<double> edges(n_mels + 2);
+  const double m0 = to_mel(lo), m1 = to_mel(hi), estep = (m1 - m0) / (n_mels + 1);
+  for (int i = 0; i < n_mels + 2; ++i) edges[i] = to_hz(i == n_mels + 1 ? m1 : m0 + i * estep);
+  const double bstep = n_bins > 1 ? nyq / (n_bins - 1) : 0.0;
+  w->assign((size_t)n_bins * n_mels, 0.0);
+  for (int m = 0; m < n_mels; ++m) {
+    const double l = edges[m], c = edges[m + 1], u = edges[m + 2];
+    const double scale = norm ? 2.0 / (u - l) : 1.0;
+    for (int k = 0; k < n_bins; ++k) {  // DC kept
+      const double f = k == n_bins - 1 ? nyq : k * bstep;
+      (*w)[(size_t)k * n_mels + m] = scale * std::max(0.0, std::min((f - l) / (c - l), (u - f) / (u - c)));
+    }
+  }
+  return A2M_OK;
+}
+
 // ------------------------------------------------------------------------------ device
 __device__ __forceinline__ float2 cmul(float2 a, float2 b) {
   return make_float2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x);
 }
 
+// Launch state of the PATS front ends (a2m_pats_audio_f32); unused by the VGGish ones.
+struct PatsArgs {
+  int64_t n_samples;         // per clip
+  const int64_t* frame_ids;  // output row -> clip * n_frames + frame (null: the identity)
+  int64_t n_src;             // n_clips * n_frames; an id outside [0, n_src) gives a NaN row
+  int pad;                   // samples of padding ahead of frame 0 (centred: fft_len / 2)
+  int pad_zero;              // 1: the padding is zeros, 0: the clip mirrored about its end samples
+  int lead;                  // zeros ahead of the window inside the frame: (fft_len - window) / 2
+  int power;                 // 2: |X|^2, 1: |X|
+  float log_eps;             // ln(eps) rounded once on the host: the value of a masked zero
+  const float* mean;         // optional standardisation of the output, as a2m_window_gather_f32
+  const float* std_;
+};
+
+// Sample p of the padded clip for p outside [0, S): only frames that touch a pad come here.
+// Reflection needs pad < S (host check), so one mirror lands inside; the clamp keeps a bad
+// caller in bounds.
+__device__ __forceinline__ float edge_sample(const float* __restrict__ clip, int64_t p, int64_t S,
+                                             bool pad_zero) {
+  if (p < 0 || p >= S) {
+    if (pad_zero) return 0.f;
+    p = p < 0 ? -p : 2 * (S - 1) - p;
+    p = p < 0 ? 0 : p >= S ? S - 1 : p;
+  }
+  return clip[p];
+}
+
+// Where output row `row` reads: its clip, the padded-clip index of its first sample, whether all
+// fft_len samples are inside the clip.  !valid marks a row to fill with NaN.
+struct FrameSrc {
+  const float* clip;
+  int64_t start;
+  bool interior, valid;
+};
+__device__ __forceinline__ FrameSrc pats_frame(const float* __restrict__ wave, int64_t clip_stride,
+                                               int n_frames, int hop, int nfft, int64_t row,
+                                               const PatsArgs& pa) {
+  int64_t id = pa.frame_ids ? pa.frame_ids[row] : row;
+  FrameSrc f;
+  f.valid = id >= 0 && id < pa.n_src;
+  const uint32_t id32 = f.valid ? (uint32_t)id : 0u;  // n_src < 2^31 (host check)
+  const uint32_t clip = id32 / (uint32_t)n_frames;
+  f.clip = wave + clip * clip_stride;
+  f.start = (int64_t)(id32 - clip * (uint32_t)n_frames) * hop - pa.pad;
+  f.interior = f.start >= 0 && f.start + nfft <= pa.n_samples;
+  return f;
+}
+
+// zero mask, natural log, optional standardisation (evaluation.hip window_gather_kernel's)
+__device__ __forceinline__ float pats_epilogue(float acc, int m, const PatsArgs& pa) {
+  float v = acc == 0.f ? pa.log_eps : logf(acc);
+  if (pa.mean) {
+    const float s = pa.std_[m] < 1e-7f ? 1.f : pa.std_[m];
+    v = __fdiv_rn(__fsub_rn(v, pa.mean[m]), s);
+  }
+  return v;
+}
+
+template <bool PATS>  // log_offset: the VGGish offset added before the log (PATS: see PatsArgs::log_eps)
 __global__ __launch_bounds__(256) void logmel_kernel(const float* __restrict__ wave,
                                                      int64_t clip_stride, int n_frames,
                                                      const unsigned char* __restrict__ plan,
-                                                     float log_offset, float* __restrict__ out) {
+                                                     float log_offset, float* __restrict__ out,
+                                                     PatsArgs pa) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const PlanHeader* ph = reinterpret_cast<const PlanHeader*>(plan);
   const int win = ph->window, hop = ph->hop, nfft = ph->fft_len, n_mels = ph->n_mels;
@@ -115,6 +215,8 @@ __global__ __launch_bounds__(256) void logmel_kernel(const float* __restrict__ w
   const int frame = blockIdx.x % n_frames;
   const int clip = blockIdx.x / n_frames;
   const float* src = wave + clip * clip_stride + (int64_t)frame * hop;
+  FrameSrc fs{};
+  if (PATS) fs = pats_frame(wave, clip_stride, n_frames, hop, nfft, blockIdx.x, pa);
   float* xs = reinterpret_cast<float*>(buf0);
   // all of this thread's sample (and window) loads are issued before the first LDS write
   // (a blockDim-strided loop would wait for each load in turn)
@@ -123,6 +225,14 @@ __global__ __launch_bounds__(256) void logmel_kernel(const float* __restrict__ w
 #pragma unroll
   for (int j = 0; j < PF; ++j) {
     const int n = threadIdx.x + j * 256;
+    if (PATS) {  // the frame spans fft_len samples, the window sits at [lead, lead + win)
+      const int wn = n - pa.lead;
+      const bool in = wn >= 0 && wn < win && n < nfft;
+      sv[j] = !in ? 0.f : fs.interior ? fs.clip[fs.start + n]
+                                      : edge_sample(fs.clip, fs.start + n, pa.n_samples, pa.pad_zero);
+      wv[j] = in ? window[wn] : 0.f;
+      continue;
+    }
     const bool in = n < win && n < nfft;
     sv[j] = in ? src[n] : 0.f;
     wv[j] = in ? window[n] : 0.f;
@@ -178,18 +288,21 @@ __global__ __launch_bounds__(256) void logmel_kernel(const float* __restrict__ w
     const float2 o = make_float2(0.5f * dd.y, -0.5f * dd.x);   // / (2i)
     const float2 wo = cmul(tw[k], o);
     const float re = e.x + wo.x, im = e.y + wo.y;
-    mag[k] = sqrtf(re * re + im * im);
+    mag[k] = PATS && pa.power == 2 ? re * re + im * im : sqrtf(re * re + im * im);
   }
   __syncthreads();
 
-  float* dst = out + ((int64_t)clip * n_frames + frame) * n_mels;
+  float* dst = out + (PATS ? (int64_t)blockIdx.x : (int64_t)clip * n_frames + frame) * n_mels;
   for (int m = threadIdx.x; m < n_mels; m += blockDim.x) {
     const int s = mstart[m], len = mlen[m];
     const float* wp = mw + mwoff[m];
     float acc = 0.f;
 #pragma unroll 8
     for (int q = 0; q < len; ++q) acc += wp[q] * mag[s + q];
-    dst[m] = logf(acc + log_offset);
+    if (PATS)
+      dst[m] = fs.valid ? pats_epilogue(acc, m, pa) : __builtin_nanf("");
+    else
+      dst[m] = logf(acc + log_offset);
   }
 }
 
@@ -332,18 +445,22 @@ constexpr int LM_MAX_W4 = 64 * LM_ROWS;
 //   mel      lane owns bands lane and 127 - lane (narrow + wide: balanced), rows aligned to
 //            4 bins so weights and magnitudes are both read as float4
 // then log(mel + offset).  LDS per wave: 8.7 KB; the mel rows once per workgroup.
+// PATS (window == 2048 only): the wave's frame comes from pats_frame (frame map, centring); a
+// frame that touches a pad loads through edge_sample, every other frame exactly as FULL does;
+// power == 2 drops the square roots (the values are then 4 |X|^2, the mel rows carry the 1/4).
 // ---------------------------------------------------------------------------------------
-template <bool FULL>  // FULL: window == fft_len == 2048 (Hann from twiddles, no predicated loads)
+template <bool FULL, bool PATS>  // FULL: window == fft_len == 2048 (Hann from twiddles, no predicated loads)
 __global__ __launch_bounds__(64 * LM_WAVES) void logmel2048_kernel(
     const float* __restrict__ wave, int64_t clip_stride, int n_frames, int total_frames,
-    const unsigned char* __restrict__ plan, float log_offset, float* __restrict__ out) {
+    const unsigned char* __restrict__ plan, float log_offset, float* __restrict__ out, PatsArgs pa) {
+  static_assert(FULL || !PATS, "the PATS register path is the full-window one");
   constexpr int M = 1024;
   __shared__ f2 s_region[LM_WAVES][LM_REGION];
   __shared__ float4 s_w4[LM_MAX_W4];
   const PlanHeader* ph = reinterpret_cast<const PlanHeader*>(plan);
   const int win = ph->window, hop = ph->hop, n_mels = ph->n_mels, n_w4 = ph->n_w4;
   const int la = ph->la, lb = ph->lb;
-  const bool lds_rows = la + lb <= LM_ROWS;      // else the mel rows are read from L2
+  const bool lds_rows = PATS || la + lb <= LM_ROWS;  // else the mel rows are read from L2 (PATS: they always fit)
   const float* window = reinterpret_cast<const float*>(plan + ph->off_window);
   const f2* tw = reinterpret_cast<const f2*>(plan + ph->off_twiddle);   // W2048^t
   const int4* band = reinterpret_cast<const int4*>(plan + ph->off_band);
@@ -355,6 +472,12 @@ __global__ __launch_bounds__(64 * LM_WAVES) void logmel2048_kernel(
   const int frame = active ? gframe % n_frames : 0;
   const int clip = active ? gframe / n_frames : 0;
   const float* src = wave + clip * clip_stride + (int64_t)frame * hop;
+  FrameSrc fs{};
+  if (PATS) {  // read once per wave: the row index is wave-uniform
+    const int row = __builtin_amdgcn_readfirstlane(active ? gframe : 0);
+    fs = pats_frame(wave, clip_stride, n_frames, hop, 2 * M, row, pa);
+    src = fs.clip + fs.start;  // dereferenced by interior frames only
+  }
   f2* sx = s_region[wv];
 
   // mel weight rows: one copy per workgroup in LDS (loads issued before the frame's samples)
@@ -377,11 +500,20 @@ __global__ __launch_bounds__(64 * LM_WAVES) void logmel2048_kernel(
   f2 v[16];
   {
     f2 x[16], w[16];
+    const bool edge = PATS && !fs.interior;  // wave-uniform: only frames that touch a pad
+    if (edge) {
+#pragma unroll
+      for (int j = 0; j < 16; ++j) {
+        const int64_t p = fs.start + 2 * (lane + 64 * j);
+        x[j] = (f2){edge_sample(fs.clip, p, pa.n_samples, pa.pad_zero),
+                    edge_sample(fs.clip, p + 1, pa.n_samples, pa.pad_zero)};
+      }
+    }
 #pragma unroll
     for (int j = 0; j < 16; ++j) {
       const int n = 2 * (lane + 64 * j);
       if (FULL) {  // 0.5 - 0.5 cos(2 pi n / 2048) = 0.5 - 0.5 Re(W1024^lane W16^j [W2048])
-        x[j] = (f2){src[n], src[n + 1]};
+        if (!edge) x[j] = (f2){src[n], src[n + 1]};
         const f2 cre = (f2){HANN_C0_RE[j], HANN_C1_RE[j]}, cim = (f2){HANN_C0_IM[j], HANN_C1_IM[j]};
         const f2 r = __builtin_elementwise_fma(-b1.yy, cim, b1.xx * cre);
         w[j] = __builtin_elementwise_fma((f2)(-0.5f), r, (f2)(0.5f));
@@ -450,14 +582,15 @@ __global__ __launch_bounds__(64 * LM_WAVES) void logmel2048_kernel(
       const f2 wd = pmul(w, d);                  // X2 = s -+ i wd
       const f2 xa = add_mi(s, wd), xb = sub_mi(s, wd);
       const f2 qa = xa * xa, qb = xb * xb;
-      mg[8 * u + 2 * k3] = __builtin_amdgcn_sqrtf(qa.x + qa.y);
-      mg[8 * u + 2 * k3 + 1] = __builtin_amdgcn_sqrtf(qb.x + qb.y);
+      const bool pw = PATS && pa.power == 2;
+      mg[8 * u + 2 * k3] = pw ? qa.x + qa.y : __builtin_amdgcn_sqrtf(qa.x + qa.y);
+      mg[8 * u + 2 * k3 + 1] = pw ? qb.x + qb.y : __builtin_amdgcn_sqrtf(qb.x + qb.y);
       ki[8 * u + 2 * k3] = ka;
       ki[8 * u + 2 * k3 + 1] = M - ka;
     }
     if (u == 1) {  // lane 63 also owns X[512] = |Z[512]| (stored x2 like the others)
       const f2 q = za[2] * za[2];
-      mg[16] = 2.f * __builtin_amdgcn_sqrtf(q.x + q.y);
+      mg[16] = PATS && pa.power == 2 ? 4.f * (q.x + q.y) : 2.f * __builtin_amdgcn_sqrtf(q.x + q.y);
       ki[16] = 512;
     }
   }
@@ -476,7 +609,21 @@ __global__ __launch_bounds__(64 * LM_WAVES) void logmel2048_kernel(
   if (!active) return;
   const int stA = bd.x, stB = bd.y, r0 = lane * (la + lb);
   f2 accA = (f2)(0.f), accB = (f2)(0.f);
-  if (lds_rows) {
+  if (PATS) {  // compact rows (pack_plan): this lane's own start and counts
+    const int na = bd.w & 0xffff, nb = bd.w >> 16;
+    const float4* rowA = s_w4 + bd.z;
+    const float4* rowB = rowA + na;
+    for (int c = 0; c < na; ++c) {
+      const float4 wq = rowA[c], mq = *reinterpret_cast<const float4*>(s_mag + stA + 4 * c);
+      accA = __builtin_elementwise_fma((f2){wq.x, wq.y}, (f2){mq.x, mq.y}, accA);
+      accA = __builtin_elementwise_fma((f2){wq.z, wq.w}, (f2){mq.z, mq.w}, accA);
+    }
+    for (int c = 0; c < nb; ++c) {
+      const float4 wq = rowB[c], mq = *reinterpret_cast<const float4*>(s_mag + stB + 4 * c);
+      accB = __builtin_elementwise_fma((f2){wq.x, wq.y}, (f2){mq.x, mq.y}, accB);
+      accB = __builtin_elementwise_fma((f2){wq.z, wq.w}, (f2){mq.z, mq.w}, accB);
+    }
+  } else if (lds_rows) {
     for (int c = 0; c < la; ++c) {
       const float4 wq = s_w4[r0 + c], mq = *reinterpret_cast<const float4*>(s_mag + stA + 4 * c);
       accA = __builtin_elementwise_fma((f2){wq.x, wq.y}, (f2){mq.x, mq.y}, accA);
@@ -501,6 +648,13 @@ __global__ __launch_bounds__(64 * LM_WAVES) void logmel2048_kernel(
   }
   float* dst = out + (int64_t)gframe * n_mels;
   const int mA = lane, mB = 127 - lane;
+  if (PATS) {
+    const float nan = __builtin_nanf("");
+    if (mA < n_mels) dst[mA] = fs.valid ? pats_epilogue(accA.x + accA.y, mA, pa) : nan;
+    if (mB >= 64 && mB < n_mels)
+      dst[mB] = fs.valid ? pats_epilogue(accB.x + accB.y, mB, pa) : nan;
+    return;
+  }
   if (mA < n_mels) dst[mA] = __logf(accA.x + accA.y + log_offset);
   if (mB >= 64 && mB < n_mels) dst[mB] = __logf(accB.x + accB.y + log_offset);
 }
@@ -527,15 +681,12 @@ int a2m_logmel_geometry(int32_t sample_rate, double window_secs, double hop_secs
   return A2M_OK;
 }
 
-static int build_plan(int32_t sr, double win_s, double hop_s, int32_t n_mels, double lo, double hi,
-                      void* host, size_t bytes, size_t* need) {
-  int win, hop, nfft;
-  A2M_CHECK_ARG(geometry(sr, win_s, hop_s, &win, &hop, &nfft), "logmel: unsupported geometry");
-  A2M_CHECK_ARG(n_mels > 0 && n_mels <= 4096, "logmel: bad n_mels %d", n_mels);
+// Lays the plan out from the dense weights w[k * n_mels + m].  row_scale: what the register
+// path's mel rows are multiplied by (its spectrum values are 2 |X|, or 4 |X|^2 in power mode).
+// compact: that path's rows are stored back to back at their own lengths (the PATS kernels).
+static int pack_plan(int win, int hop, int nfft, int n_mels, const std::vector<double>& w,
+                     float row_scale, bool compact, void* host, size_t bytes, size_t* need) {
   const int n_bins = nfft / 2 + 1;
-  std::vector<double> w;
-  int rc = mel_weights(n_mels, n_bins, sr, lo, hi, &w);
-  if (rc) return rc;
   std::vector<int32_t> start(n_mels), len(n_mels), woff(n_mels);
   std::vector<float> vals;
   for (int m = 0; m < n_mels; ++m) {
@@ -558,7 +709,19 @@ static int build_plan(int32_t sr, double win_s, double hop_s, int32_t n_mels, do
     la = std::max(la, row4(l));
     lb = std::max(lb, row4(127 - l));
   }
-  const int n_w4 = 64 * (la + lb);
+  // compact: no padding to la / lb.  The Slaney rows of the top bands are four times as wide
+  // as the bottom ones', so padded rows (16 float4s per lane at 16 kHz) would not fit the LM_ROWS
+  // the kernel keeps in LDS; back to back they always do: a bin lies under at most two
+  // triangles, so nnz <= 2 * 1025 and the rows take <= (nnz + 6 * 128) / 4 < 64 * LM_ROWS float4s
+  int n_w4 = 64 * (la + lb);
+  if (compact) {
+    n_w4 = 0;
+    for (int m = 0; m < 128; ++m) n_w4 += row4(m);
+    if (nfft == 2048 && n_mels <= 128 && n_w4 > LM_MAX_W4) {
+      set_error("mel rows need %d float4s, the kernel holds %d", n_w4, LM_MAX_W4);
+      return A2M_EINVAL;
+    }
+  }
   size_t total;
   plan_layout(win, nfft, n_mels, h.nnz, n_w4, &h, &total);
   h.la = la;
@@ -596,17 +759,24 @@ static int build_plan(int32_t sr, double win_s, double hop_s, int32_t n_mels, do
   }
   if (nfft == 2048 && n_mels <= 128) {
     // band[lane] = {A start, B start, 0, 0} (starts rounded down to a multiple of 4); rows of
-    // lane l at float4 l (la + lb): A then B; weights x 0.5 (the kernel's magnitudes are 2 |X|)
+    // lane l at float4 l (la + lb): A then B; weights x row_scale (0.5: the kernel's magnitudes are 2 |X|)
+    // compact: band[lane] = {A start, B start, first float4 of the lane's rows, A | B << 16 float4s}
     int32_t* band = reinterpret_cast<int32_t*>(p + h.off_band);
     float* w4 = reinterpret_cast<float*>(p + h.off_w4);
+    int next = 0;
     for (int lane = 0; lane < 64; ++lane) {
+      if (compact) {
+        band[4 * lane + 2] = next;
+        band[4 * lane + 3] = row4(lane) | row4(127 - lane) << 16;
+      }
       for (int half = 0; half < 2; ++half) {
         const int m = half == 0 ? lane : 127 - lane;
         const int l4 = row4(m);
         const int st4 = l4 ? start[m] & ~3 : 0;
         band[4 * lane + half] = st4;
-        float* row = w4 + 4 * (lane * (la + lb) + (half == 0 ? 0 : la));
-        for (int q = 0; q < (l4 ? len[m] : 0); ++q) row[(start[m] - st4) + q] = 0.5f * vals[woff[m] + q];
+        float* row = w4 + 4 * (compact ? next : lane * (la + lb) + (half == 0 ? 0 : la));
+        next += l4;
+        for (int q = 0; q < (l4 ? len[m] : 0); ++q) row[(start[m] - st4) + q] = row_scale * vals[woff[m] + q];
       }
     }
   }
@@ -615,6 +785,17 @@ static int build_plan(int32_t sr, double win_s, double hop_s, int32_t n_mels, do
   std::memcpy(p + h.off_woff, woff.data(), sizeof(int32_t) * n_mels);
   if (!vals.empty()) std::memcpy(p + h.off_weights, vals.data(), sizeof(float) * vals.size());
   return A2M_OK;
+}
+
+static int build_plan(int32_t sr, double win_s, double hop_s, int32_t n_mels, double lo, double hi,
+                      void* host, size_t bytes, size_t* need) {
+  int win, hop, nfft;
+  A2M_CHECK_ARG(geometry(sr, win_s, hop_s, &win, &hop, &nfft), "logmel: unsupported geometry");
+  A2M_CHECK_ARG(n_mels > 0 && n_mels <= 4096, "logmel: bad n_mels %d", n_mels);
+  std::vector<double> w;
+  int rc = mel_weights(n_mels, nfft / 2 + 1, sr, lo, hi, &w);
+  if (rc) return rc;
+  return pack_plan(win, hop, nfft, n_mels, w, 0.5f, false, host, bytes, need);
 }
 
 size_t a2m_logmel_plan_bytes(int32_t sample_rate, double window_secs, double hop_secs,
@@ -648,17 +829,126 @@ int a2m_logmel_f32(const float* wave, int64_t n_clips, int64_t clip_stride, int6
   // register-FFT path (its mel rows sit in LDS when each lane's fit in LM_ROWS float4s, as
   // for the build configuration, and are read from L2 otherwise)
   if (fft_len == 2048 && n_mels <= 128) {
-    auto kern = window == 2048 ? logmel2048_kernel<true> : logmel2048_kernel<false>;
+    auto kern = window == 2048 ? logmel2048_kernel<true, false> : logmel2048_kernel<false, false>;
     const int64_t total = n_clips * nf;
     hipLaunchKernelGGL(kern, dim3((unsigned)cdiv(total, LM_WAVES)), dim3(64 * LM_WAVES), 0,
                        as_stream(stream), wave, clip_stride, (int)nf, (int)total,
-                       static_cast<const unsigned char*>(dev_plan), log_offset, out);
+                       static_cast<const unsigned char*>(dev_plan), log_offset, out, PatsArgs{});
     A2M_LAUNCH_CHECK();
     return A2M_OK;
   }
-  hipLaunchKernelGGL(logmel_kernel, dim3((unsigned)(n_clips * nf)), dim3(256), lds,
+  hipLaunchKernelGGL(logmel_kernel<false>, dim3((unsigned)(n_clips * nf)), dim3(256), lds,
                      as_stream(stream), wave, clip_stride, (int)nf,
-                     static_cast<const unsigned char*>(dev_plan), log_offset, out);
+                     static_cast<const unsigned char*>(dev_plan), log_offset, out, PatsArgs{});
+  A2M_LAUNCH_CHECK();
+  return A2M_OK;
+}
+
+// ------------------------------------------------------------------------ PATS front ends
+static int pats_plan(int32_t sr, int32_t n_fft, int32_t hop, int32_t win_length, int32_t n_mels,
+                     double fmin, double fmax, int32_t slaney_norm, int32_t power, void* host,
+                     size_t bytes, size_t* need) {
+  A2M_CHECK_ARG(sr > 0 && n_fft >= 4 && n_fft <= 4096 && (n_fft & (n_fft - 1)) == 0,
+                "pats_audio: n_fft %d must be a power of two in [4, 4096]", n_fft);
+  A2M_CHECK_ARG(hop > 0 && win_length >= 2 && win_length <= n_fft,
+                "pats_audio: bad hop %d / win_length %d for n_fft %d", hop, win_length, n_fft);
+  A2M_CHECK_ARG(n_mels > 0 && n_mels <= 4096, "pats_audio: bad n_mels %d", n_mels);
+  A2M_CHECK_ARG(power == 1 || power == 2, "pats_audio: power %d must be 1 or 2", power);
+  std::vector<double> w;
+  int rc = slaney_weights(n_mels, n_fft / 2 + 1, sr, fmin, fmax, slaney_norm != 0, &w);
+  if (rc) return rc;
+  return pack_plan(win_length, hop, n_fft, n_mels, w, power == 2 ? 0.25f : 0.5f, true, host, bytes, need);
+}
+
+size_t a2m_pats_audio_plan_bytes(int32_t sample_rate, int32_t n_fft, int32_t hop, int32_t win_length,
+                                 int32_t n_mels, double fmin, double fmax, int32_t slaney_norm,
+                                 int32_t power) {
+  size_t need = 0;
+  if (pats_plan(sample_rate, n_fft, hop, win_length, n_mels, fmin, fmax, slaney_norm, power, nullptr,
+                0, &need))
+    return 0;
+  return need;
+}
+
+int a2m_pats_audio_plan_build(int32_t sample_rate, int32_t n_fft, int32_t hop, int32_t win_length,
+                              int32_t n_mels, double fmin, double fmax, int32_t slaney_norm,
+                              int32_t power, void* host_plan, size_t plan_bytes) {
+  size_t need = 0;
+  return pats_plan(sample_rate, n_fft, hop, win_length, n_mels, fmin, fmax, slaney_norm, power,
+                   host_plan, plan_bytes, &need);
+}
+
+int a2m_pats_audio_plan_filterbank(const void* host_plan, size_t plan_bytes, float* basis) {
+  A2M_CHECK_ARG(host_plan && basis && plan_bytes >= sizeof(PlanHeader), "pats_audio: bad plan");
+  const unsigned char* p = static_cast<const unsigned char*>(host_plan);
+  PlanHeader h;
+  std::memcpy(&h, p, sizeof(h));
+  A2M_CHECK_ARG(h.n_mels > 0 && h.n_bins == h.fft_len / 2 + 1 && h.nnz >= 0 &&
+                    (size_t)h.off_weights + sizeof(float) * (size_t)h.nnz <= plan_bytes,
+                "pats_audio: bad plan");
+  const int32_t* start = reinterpret_cast<const int32_t*>(p + h.off_start);
+  const int32_t* len = reinterpret_cast<const int32_t*>(p + h.off_len);
+  const int32_t* woff = reinterpret_cast<const int32_t*>(p + h.off_woff);
+  const float* vals = reinterpret_cast<const float*>(p + h.off_weights);
+  std::memset(basis, 0, sizeof(float) * (size_t)h.n_mels * h.n_bins);
+  for (int m = 0; m < h.n_mels; ++m)
+    for (int q = 0; q < len[m]; ++q) basis[(size_t)m * h.n_bins + start[m] + q] = vals[woff[m] + q];
+  return A2M_OK;
+}
+
+int64_t a2m_pats_audio_num_frames(int64_t n_samples, int32_t n_fft, int32_t hop, int32_t center) {
+  if (hop <= 0 || n_fft <= 0 || n_samples < 0) return 0;
+  const int64_t padded = n_samples + (center ? 2 * (int64_t)(n_fft / 2) : 0);
+  return padded < n_fft ? 0 : 1 + (padded - n_fft) / hop;
+}
+
+int a2m_pats_audio_f32(const float* wave, int64_t n_clips, int64_t clip_stride, int64_t n_samples,
+                       int32_t n_fft, int32_t hop, int32_t win_length, int32_t n_mels, int32_t power,
+                       const void* dev_plan, int32_t center, int32_t pad_mode, float eps,
+                       const int64_t* frame_ids, int64_t n_out, const float* mean, const float* std_,
+                       float* out, void* stream) {
+  A2M_CHECK_ARG(n_fft >= 4 && n_fft <= 4096 && (n_fft & (n_fft - 1)) == 0 && hop > 0 &&
+                    win_length >= 2 && win_length <= n_fft,
+                "pats_audio: bad geometry n_fft=%d hop=%d win_length=%d", n_fft, hop, win_length);
+  A2M_CHECK_ARG(power == 1 || power == 2, "pats_audio: power %d must be 1 or 2", power);
+  A2M_CHECK_ARG(pad_mode == A2M_PAD_REFLECT || pad_mode == A2M_PAD_CONSTANT,
+                "pats_audio: pad_mode %d is neither reflect nor constant", pad_mode);
+  A2M_CHECK_ARG(n_clips >= 0 && n_samples >= 0 && n_out >= 0 && n_mels > 0, "pats_audio: bad sizes");
+  A2M_CHECK_ARG(eps > 0.f, "pats_audio: eps %g must be positive", (double)eps);
+  A2M_CHECK_ARG((mean == nullptr) == (std_ == nullptr), "pats_audio: mean and std come together");
+  A2M_CHECK_ARG(!center || pad_mode != A2M_PAD_REFLECT || n_samples > n_fft / 2,
+                "pats_audio: reflect padding needs more than n_fft / 2 = %d samples, got %lld",
+                n_fft / 2, (long long)n_samples);
+  const int64_t nf = a2m_pats_audio_num_frames(n_samples, n_fft, hop, center);
+  const int64_t total = frame_ids ? n_out : n_clips * nf;
+  A2M_CHECK_ARG(frame_ids || n_out == n_clips * nf, "pats_audio: n_out %lld != n_clips * n_frames %lld",
+                (long long)n_out, (long long)(n_clips * nf));
+  if (total == 0) return A2M_OK;  // empty output, like the reference's (0, n_mels)
+  A2M_CHECK_ARG(wave && out && dev_plan, "pats_audio: null pointer");
+  A2M_CHECK_ARG(nf > 0 && n_clips > 0, "pats_audio: a frame map over a wave without frames");
+  A2M_CHECK_ARG(total < (1LL << 31) && n_clips * nf < (1LL << 31), "pats_audio: too many frames");
+  PatsArgs pa{};
+  pa.n_samples = n_samples;
+  pa.frame_ids = frame_ids;
+  pa.n_src = n_clips * nf;
+  pa.pad = center ? n_fft / 2 : 0;
+  pa.pad_zero = pad_mode == A2M_PAD_CONSTANT;
+  pa.lead = (n_fft - win_length) / 2;
+  pa.power = power;
+  pa.log_eps = (float)std::log((double)eps);
+  pa.mean = mean;
+  pa.std_ = std_;
+  const unsigned char* plan = static_cast<const unsigned char*>(dev_plan);
+  if (n_fft == 2048 && win_length == 2048 && n_mels <= 128) {  // register FFT, one wave per frame
+    hipLaunchKernelGGL((logmel2048_kernel<true, true>), dim3((unsigned)cdiv(total, LM_WAVES)),
+                       dim3(64 * LM_WAVES), 0, as_stream(stream), wave, clip_stride, (int)nf,
+                       (int)total, plan, eps, out, pa);
+    A2M_LAUNCH_CHECK();
+    return A2M_OK;
+  }
+  const size_t lds = sizeof(float) * (2 * (size_t)n_fft + n_fft / 2 + 1 + 3);
+  hipLaunchKernelGGL(logmel_kernel<true>, dim3((unsigned)total), dim3(256), lds, as_stream(stream),
+                     wave, clip_stride, (int)nf, plan, eps, out, pa);
   A2M_LAUNCH_CHECK();
   return A2M_OK;
 }

@@ -58,6 +58,41 @@ int a2m_logmel_f32(const float* wave, int64_t n_clips, int64_t clip_stride, int6
                    int32_t window, int32_t hop, int32_t fft_len, int32_t n_mels,
                    const void* dev_plan, float log_offset, float* out, void* stream);
 
+/* ---------------------------------------------------------------- PATS audio features
+ * audio/log_mel_512 and audio/log_mel_400 from a waveform (pats/data_loading/audio.py:58-120),
+ * i.e. librosa.feature.melspectrogram: frames of n_fft samples every `hop`, a periodic Hann of
+ * win_length centred in the frame, |rfft|^power (1 or 2, DC kept), a Slaney mel filterbank
+ * (htk=False; slaney_norm != 0 scales each triangle to unit area), exact zeros replaced by eps,
+ * natural log.  The plan is built on the HOST in float64 and copied to the device by the caller,
+ * like the a2m_logmel_* one; bad band edges (fmax above Nyquist, ...) give A2M_EINVAL.
+ *   log_mel_512: n_fft 2048, hop 512, win_length 2048, 128 mels, 0..sr/2, norm, power 2, centred
+ *   log_mel_400: sr 16000, n_fft 512, hop 160, win_length 400, 64 mels, 125..7500, no norm,
+ *                power 1, not centred */
+#define A2M_PAD_REFLECT 0  /* numpy.pad 'reflect': mirrored without repeating the edge sample */
+#define A2M_PAD_CONSTANT 1 /* zeros */
+size_t a2m_pats_audio_plan_bytes(int32_t sample_rate, int32_t n_fft, int32_t hop, int32_t win_length,
+                                 int32_t n_mels, double fmin, double fmax, int32_t slaney_norm,
+                                 int32_t power);
+int a2m_pats_audio_plan_build(int32_t sample_rate, int32_t n_fft, int32_t hop, int32_t win_length,
+                              int32_t n_mels, double fmin, double fmax, int32_t slaney_norm,
+                              int32_t power, void* host_plan, size_t plan_bytes);
+/* the plan's filterbank as a dense basis[n_mels][1 + n_fft/2] (what librosa.filters.mel returns) */
+int a2m_pats_audio_plan_filterbank(const void* host_plan, size_t plan_bytes, float* basis);
+/* center != 0: n_fft/2 samples of padding on both sides, 1 + n_samples / hop frames;
+ * otherwise 1 + (n_samples - n_fft) / hop, and 0 below n_fft samples */
+int64_t a2m_pats_audio_num_frames(int64_t n_samples, int32_t n_fft, int32_t hop, int32_t center);
+/* wave as for a2m_logmel_f32.  frame_ids == NULL: out[c][f][m], n_out = n_clips * n_frames.
+ * Otherwise row r of out[n_out][n_mels] is source frame frame_ids[r] = clip * n_frames + frame
+ * (device int64; an id out of range gives a row of NaN), so a window gather computes only the
+ * frames it reads.  mean / std (both or neither, [n_mels]) standardise the output as
+ * a2m_window_gather_f32 does.  Reflect padding needs n_samples > n_fft / 2.  No host
+ * synchronisation: capturable into a HIP graph. */
+int a2m_pats_audio_f32(const float* wave, int64_t n_clips, int64_t clip_stride, int64_t n_samples,
+                       int32_t n_fft, int32_t hop, int32_t win_length, int32_t n_mels, int32_t power,
+                       const void* dev_plan, int32_t center, int32_t pad_mode, float eps,
+                       const int64_t* frame_ids, int64_t n_out, const float* mean, const float* std_,
+                       float* out, void* stream);
+
 /* ---------------------------------------------------------------- convolutions
  * ConvNormRelu (model_layers.py:51-118) forward in eval mode: conv + bias, optional
  * BatchNorm (running stats; bn_w == NULL disables it), activation (A2M_ACT_*, LeakyReLU
