@@ -139,6 +139,7 @@ SIGNATURES = {
     'a2m_gemm_timing_begin': (ctypes.c_int, []),
     'a2m_gemm_plan_override': (ctypes.c_int, [I32, I32]),
     'a2m_gemm_pipe_override': (ctypes.c_int, [I32]),
+    'a2m_convt_pair_override': (ctypes.c_int, [I32]),
     'a2m_set_gemm_precision': (ctypes.c_int, [I32]),
     'a2m_set_attn_eval_chunk': (ctypes.c_int, [I32]),
     'a2m_get_gemm_precision': (I32, []),

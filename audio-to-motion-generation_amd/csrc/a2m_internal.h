@@ -127,6 +127,12 @@ int gemm_k_tile();
 int gemm(const Gather& A, const Gather& B, const Epilogue& E, int M, int N, int K, int batch,
          void* ws, size_t ws_bytes, hipStream_t stream, int force_split = 0);
 size_t gemm_ws_bytes(int M, int N, int K, int batch);
+// Two independent tap-chunked (mode 5) problems of equal M and N -- the two output phases of a
+// stride-2 ConvTranspose1d -- as one launch, each at one split (gemm.hip).  Returns
+// kGemmPairNotTaken where the pair is not eligible: the caller then issues the two gemm() calls.
+constexpr int kGemmPairNotTaken = 1;
+int gemm_pair(const Gather& A0, const Gather& B0, const Epilogue& E0, int K0, const Gather& A1,
+              const Gather& B1, const Epilogue& E1, int K1, int M, int N, hipStream_t stream);
 
 // shared host-side launch helpers (defined next to their kernels)
 int softmax_rows(float* x, int rows, int n, hipStream_t st);                       // ops.hip

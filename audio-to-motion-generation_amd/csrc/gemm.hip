@@ -327,6 +327,7 @@ static int gemm_xcd_group() { return 8; }
 
 static int g_override_tile = 0, g_override_split = 0;   // a2m_gemm_plan_override (tuning)
 static int g_pipe_override = -1;   // a2m_gemm_pipe_override: -1 default (pipelined), 0 gemm_tile, 1 pipelined
+static int g_pair_override = -1;   // a2m_convt_pair_override: -1 default (gemm_pair's fill rule), 0 never, 1 whenever eligible
 
 struct PlanRule {
   int M, N, K, tile, splits;
@@ -570,6 +571,29 @@ static unsigned long long* timing_open(double flops, const char* desc) {
   return g_ts + kRecSlots * (g_timing_recs.size() - 1);
 }
 
+// raw buffer loads of the pipelined tiles: every element offset below 2^29 floats
+static bool pipe_below(int64_t v) { return v >= 0 && v < ((int64_t)1 << 29); }
+
+// mode 5 as the fp32 pipelined tile takes it (at a 64-row tile): 1-3 taps over clips that tile the 64 rows
+static bool pipe_tap5(const Gather& B, int mb) {
+  return mb == 5 && B.tapconv >= 1 && B.tapconv <= 3 && B.R2 % 4 == 0 && 64 % B.R2 == 0;
+}
+
+// float4 output rows (pipelined tile): n contiguous within 4-aligned groups of one n2 run, every
+// other stride and base 16-byte aligned; split-K slabs ([M][N]) whenever N % 4 == 0
+static bool epi_vec4(const Epilogue& E, int N, bool mcontig, bool slab_out) {
+  auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
+  // the innermost index that varies with n: n2 (N2 > 1), else n1 (N1 > 1), else n0
+  const int in_lvl = E.N2 > 1 ? 2 : (E.N1 > 1 ? 1 : 0);
+  const int in_stride = in_lvl == 2 ? E.so2 : (in_lvl == 1 ? E.so1 : E.so0);
+  const int in_len = in_lvl == 2 ? E.N2 : (in_lvl == 1 ? E.N1 : 4);
+  const bool outer4 = (in_lvl == 0 || E.so0 % 4 == 0) && (in_lvl != 2 || E.N1 == 1 || E.so1 % 4 == 0) &&
+                      E.som % 4 == 0 && E.bstride % 4 == 0;
+  return !mcontig && N % 4 == 0 &&
+         (slab_out || (in_stride == 1 && in_len % 4 == 0 && outer4 && al16(E.out) &&
+                       (!E.res1 || al16(E.res1)) && (!E.res2 || al16(E.res2))));
+}
+
 int gemm(const Gather& A, const Gather& B, const Epilogue& E, int M, int N, int K, int batch,
          void* ws, size_t ws_bytes, hipStream_t stream, int force_split) {
   A2M_CHECK_ARG(M > 0 && N > 0 && K >= 0 && batch > 0, "gemm: bad sizes M=%d N=%d K=%d batch=%d",
@@ -585,7 +609,7 @@ int gemm(const Gather& A, const Gather& B, const Epilogue& E, int M, int N, int 
   // gemm_tile): fp32 64x64, dense weights x dense rows / channels-last rows / halo tap conv, every
   // element offset below 2^29 floats (raw buffer loads)
   const int pipe_on = g_pipe_override >= 0 ? g_pipe_override : 1;
-  auto below = [](int64_t v) { return v >= 0 && v < ((int64_t)1 << 29); };
+  auto below = pipe_below;
   bool pipe_ext = below((int64_t)(M - 1) * A.sr0 + K);
   if (mb == 0) pipe_ext = pipe_ext && below((int64_t)(N - 1) * B.sr0 + K);
   else if (mb == 6) pipe_ext = pipe_ext && below((int64_t)((N - 1) / (B.R1 * B.R2)) * B.sr0 + (int64_t)B.Lh * B.Lw * B.nhwc);
@@ -618,7 +642,7 @@ int gemm(const Gather& A, const Gather& B, const Epilogue& E, int M, int N, int 
                        ((mb == 0 && below((int64_t)(N - 1) * B.sr0 + K)) ||
                         (rows3 && below((int64_t)((N - 1) / B.R2) * B.sr0 + B.R2 + (int64_t)K * B.sk0)));
   // the operand modes the fp32 pipelined tile takes (at a 64-row tile)
-  const bool tap5 = mb == 5 && B.tapconv >= 1 && B.tapconv <= 3 && B.R2 % 4 == 0 && 64 % B.R2 == 0;
+  const bool tap5 = pipe_tap5(B, mb);
   const bool pipe_modes = (ma == 0 && (mb == 0 || mb == 6 || rows3 || tap5) && pipe_ext) || m4_ok || pipe_a3;
   // launches the pipelined tile takes are planned on 64x64 tiles: fp32 every such launch, bf16 its
   // training modes (mode-4 / plain mode-3 A: bf16 B=32 training kernel time 43.0 -> 41.7 ms a step,
@@ -641,19 +665,7 @@ int gemm(const Gather& A, const Gather& B, const Epilogue& E, int M, int N, int 
                             (size_t)E.interp_H * sizeof(float) <= 32768),
                 "gemm: fused resample needs batch 1, N a multiple of H = %d <= 8192", E.interp_H);
   a.mcontig = E.som == 1 && M > 1 && !interp;
-  // float4 output rows (pipelined tile): n contiguous within 4-aligned groups of one n2 run, every
-  // other stride and base 16-byte aligned; split-K slabs ([M][N]) whenever N % 4 == 0
-  auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
-  const bool slab_out = p.splits > 1 || interp;
-  // the innermost index that varies with n: n2 (N2 > 1), else n1 (N1 > 1), else n0
-  const int in_lvl = E.N2 > 1 ? 2 : (E.N1 > 1 ? 1 : 0);
-  const int in_stride = in_lvl == 2 ? E.so2 : (in_lvl == 1 ? E.so1 : E.so0);
-  const int in_len = in_lvl == 2 ? E.N2 : (in_lvl == 1 ? E.N1 : 4);
-  const bool outer4 = (in_lvl == 0 || E.so0 % 4 == 0) && (in_lvl != 2 || E.N1 == 1 || E.so1 % 4 == 0) &&
-                      E.som % 4 == 0 && E.bstride % 4 == 0;
-  a.vec4 = !a.mcontig && N % 4 == 0 &&
-           (slab_out || (in_stride == 1 && in_len % 4 == 0 && outer4 && al16(E.out) &&
-                         (!E.res1 || al16(E.res1)) && (!E.res2 || al16(E.res2))));
+  a.vec4 = epi_vec4(E, N, a.mcontig, p.splits > 1 || interp);
   const bool pipe_m4 = m4_ok && p.kchunk % 32 == 0;
   const bool pipe_launch = pipe_on && prec == 0 && p.bm == 64 &&
                            ((ma == 0 && (mb == 0 || mb == 6 || rows3 || (mb == 5 && (a.B.halo || tap5))) && pipe_ext) ||
@@ -741,9 +753,82 @@ int gemm(const Gather& A, const Gather& B, const Epilogue& E, int M, int N, int 
   return A2M_OK;
 }
 
+// The two output phases of a stride-2 ConvTranspose1d as one launch of the fp32 pipelined tile
+// (gemm_pipe_kernel_pair): two mode-5 per-tap problems of equal M and N, each at one split, the one
+// with more k-steps at grid z = 0 so that the long tiles are dispatched first.  Taken only where
+// gemm() would launch the pipelined tile for both (fp32, dense packed weights, 1-3 taps over clips
+// that tile the 64 rows, offsets below 2^29, 64x64 tile) and neither epilogue is a fused
+// resample; a split count forced by a2m_gemm_plan_override / A2M_GEMM_PLAN_RULES other than 1
+// keeps the sequential path.  By default (a2m_convt_pair_override(-1)) also only where the pair
+// puts at least one block on every CU (2 tiles(M, N) >= 256): below that, split-K is how the
+// planner fills the chip, which one split per problem would undo.  Each problem's results are
+// bitwise those of its own gemm() launch at one split.  Returns kGemmPairNotTaken (the caller
+// issues the two gemm() calls) or gemm()'s status.
+int gemm_pair(const Gather& A0, const Gather& B0, const Epilogue& E0, int K0, const Gather& A1,
+              const Gather& B1, const Epilogue& E1, int K1, int M, int N, hipStream_t stream) {
+  A2M_CHECK_ARG(M > 0 && N > 0 && K0 > 0 && K1 > 0, "gemm_pair: bad sizes M=%d N=%d K=%d,%d", M, N, K0, K1);
+  const int pipe_on = g_pipe_override >= 0 ? g_pipe_override : 1;
+  if (g_pair_override == 0 || !pipe_on || g_gemm_prec != 0) return kGemmPairNotTaken;
+  if (g_pair_override < 0 && 2 * cdiv(M, 64) * cdiv(N, 64) < 256) return kGemmPairNotTaken;
+  auto eligible = [&](const Gather& A, const Gather& B, const Epilogue& E, int K) {
+    const int mb = operand_mode(B, K);
+    if (operand_mode(A, K) != 0 || !pipe_tap5(B, mb) || E.interp_T > 0) return false;
+    if (!pipe_below((int64_t)(M - 1) * A.sr0 + K) ||
+        !pipe_below((int64_t)((N - 1) / B.R2) * B.sr0 + B.R2 + (int64_t)(K / B.tapconv) * B.sk0))
+      return false;
+    const PlanRule* r = plan_rule(M, N, K);
+    if (g_override_split > 1 || (r && r->splits > 1)) return false;
+    return launch_plan(M, N, K, 1, true, 0, B.tapconv, false, 1, true).bm == 64;
+  };
+  if (!eligible(A0, B0, E0, K0) || !eligible(A1, B1, E1, K1)) return kGemmPairNotTaken;
+  GemmArgs a[2];
+  const Gather* As[2] = {&A0, &A1};
+  const Gather* Bs[2] = {&B0, &B1};
+  const Epilogue* Es[2] = {&E0, &E1};
+  const int Ks[2] = {K0, K1};
+  for (int i = 0; i < 2; ++i) {
+    GemmArgs& g = a[i];
+    g.A = *As[i]; g.B = *Bs[i]; g.E = *Es[i]; g.M = M; g.N = N; g.K = Ks[i];
+    g.B.halo = 0;   // the per-tap layout (the halo layout's results are bitwise the same)
+    g.splits = 1;
+    g.kchunk = (int)(cdiv(Ks[i], 32 * g.B.tapconv) * 32 * g.B.tapconv);
+    g.partial = nullptr;
+    g.xcd_group = gemm_xcd_group();
+    g.mcontig = g.E.som == 1 && M > 1;
+    g.vec4 = epi_vec4(g.E, N, g.mcontig, false);
+    g.ts = nullptr;
+  }
+  const int first = K1 > K0 ? 1 : 0;   // grid z = 0: the problem with more k-steps
+  static const int log_launches = env_int("A2M_GEMM_LOG", 0);
+  if (log_launches)
+    std::fprintf(stderr, "a2m gemm pair M=%d N=%d K=%d+%d tile=64 bk=32 splits=1 (pipe) taps=%d+%d\n", M, N,
+                 Ks[first], Ks[first ^ 1], a[first].B.tapconv, a[first ^ 1].B.tapconv);
+  if (g_timing) {   // one record for the pair: both problems' blocks stamp the same span slots
+    char desc[96];
+    std::snprintf(desc, sizeof(desc), "pair M=%d N=%d K=%d+%d b=1 tile=64 split=1 modes=0,5", M, N,
+                  Ks[first], Ks[first ^ 1]);
+    unsigned long long* ts = timing_open(2.0 * M * N * ((double)K0 + K1), desc);
+    if (ts) {
+      g_timing_recs.back().reduce = false;
+      static const int ready = env_int("A2M_GEMM_TIMING_READY", 0);
+      if (ready) hipLaunchKernelGGL(timing_mark_kernel, dim3(1), dim3(64), 0, stream, ts + kReadySlot);
+    }
+    a[0].ts = a[1].ts = ts;
+  }
+  launch_pipe_pair(a[first], a[first ^ 1], stream);
+  A2M_LAUNCH_CHECK();
+  return A2M_OK;
+}
+
 }  // namespace a2m
 
 extern "C" {
+
+int a2m_convt_pair_override(int32_t mode) {
+  A2M_CHECK_ARG(mode >= -1 && mode <= 1, "convt_pair_override: %d (-1 default, 0 off, 1 on)", mode);
+  a2m::g_pair_override = mode;
+  return A2M_OK;
+}
 
 int a2m_gemm_plan_override(int32_t tile, int32_t splits) {
   A2M_CHECK_ARG((tile == 0 || tile == 64 || tile == 128) && splits >= 0 && splits <= 256,

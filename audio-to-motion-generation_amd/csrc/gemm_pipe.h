@@ -386,13 +386,16 @@ __device__ __forceinline__ void pipe_epilogue_vec4(const GemmArgs& args, const f
 
 #define A2M_SB() __builtin_amdgcn_sched_barrier(0)
 
-// block -> (n-tile, m-tile, batch * split), XCD-grouped as in gemm_tile (block-uniform: SGPRs)
+// block -> (n-tile, m-tile, batch * split), XCD-grouped as in gemm_tile (block-uniform: SGPRs).
+// SLICE (the pair kernel, where grid z picks the problem): the block's problem is its own x-y
+// slice of the grid, one batch at one split, remapped within that slice
+template <bool SLICE = false>
 __device__ __forceinline__ void pipe_block(const GemmArgs& args, int& bx, int& by, int& bz) {
-  bx = blockIdx.x; by = blockIdx.y; bz = blockIdx.z;
+  bx = blockIdx.x; by = blockIdx.y; bz = SLICE ? 0 : blockIdx.z;
   if (args.xcd_group > 0) {
     const int gx = gridDim.x, gy = gridDim.y;
-    const int total = gx * gy * gridDim.z;
-    const int L = blockIdx.x + gx * (blockIdx.y + gy * blockIdx.z);
+    const int total = gx * gy * (SLICE ? 1 : gridDim.z);
+    const int L = blockIdx.x + gx * (blockIdx.y + gy * (SLICE ? 0 : blockIdx.z));
     const int q = total / 8, r = total % 8, x = L % 8;
     const int t = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + L / 8;
     bz = t / (gx * gy);
@@ -443,8 +446,13 @@ __device__ __forceinline__ void pipe_step(floatx16& acc, float (&fa0)[8], float 
   A2M_SB();
 }
 
-template <int MB, int NT = 0, int MA = 0>   // NT > 0: mode 5 in the general (per-tap store) layout
-__global__ __launch_bounds__(256) void gemm_pipe_kernel(GemmArgs args) {
+// LDS floats of a block's stages: two of A, then two of B (the halo layout's B stages are taller)
+constexpr int pipe_lds_floats(bool halo) { return 2 * 64 * kPipeLDK + 2 * (halo ? PipeHalo::HR : 64) * kPipeLDK; }
+
+// One block's tile of one problem.  lds: the block's stages (pipe_lds_floats), epr: its 64
+// epilogue rows; SLICE: see pipe_block.
+template <int MB, int NT = 0, int MA = 0, bool SLICE = false>   // NT > 0: mode 5 in the general (per-tap store) layout
+__device__ __forceinline__ void gemm_pipe_body(const GemmArgs& args, float* lds, EpiRow* epr) {
   A2M_PSTAMP(4, __builtin_amdgcn_s_memrealtime());
   A2M_PSTAMP(0, __builtin_amdgcn_s_memtime());
   span_begin(args.ts);
@@ -453,15 +461,13 @@ __global__ __launch_bounds__(256) void gemm_pipe_kernel(GemmArgs args) {
   constexpr bool TAPS = MB == 5 && NT > 0;
   constexpr int TA = BM * LDK;
   constexpr int TB = (HALO ? PipeHalo::HR : BN) * LDK;
-  __shared__ __attribute__((aligned(16))) float lds[2 * TA + 2 * TB];   // A stages, then B stages
-  __shared__ EpiRow epr[BM];
   const int tid = threadIdx.x;
   const int lane = tid & 63, wave = tid >> 6;
   const int wm = wave >> 1, wn = wave & 1;
   const int li = lane & 31, lh = lane >> 5;
 
   int bx, by, bz;
-  pipe_block(args, bx, by, bz);
+  pipe_block<SLICE>(args, bx, by, bz);
   const int zz = bz;
   const int batch = zz / args.splits, split = zz % args.splits;
   const int m0 = by * BM, n0 = bx * BN;
@@ -700,6 +706,27 @@ __global__ __launch_bounds__(256) void gemm_pipe_kernel(GemmArgs args) {
 #endif
 }
 
+template <int MB, int NT = 0, int MA = 0>
+__global__ __launch_bounds__(256) void gemm_pipe_kernel(GemmArgs args) {
+  __shared__ __attribute__((aligned(16))) float lds[pipe_lds_floats(MB == 5 && NT == 0)];
+  __shared__ EpiRow epr[64];
+  gemm_pipe_body<MB, NT, MA>(args, lds, epr);
+}
+
+// Two independent mode-5 per-tap problems of equal M and N in one launch (the two output phases
+// of a stride-2 ConvTranspose1d): grid z picks the problem, a block-uniform branch into the tile
+// body at that problem's tap count.  One split and one batch each; the blocks of the two problems
+// share nothing (each its own operands, epilogue and XCD-group remap), so a problem's results are
+// those of its own gemm_pipe_kernel<5, NT> launch whatever the dispatch order.
+template <int NT0, int NT1>
+__global__ __launch_bounds__(256) void gemm_pipe_kernel_pair(GemmArgs a0, GemmArgs a1) {
+  __shared__ __attribute__((aligned(16))) float lds[pipe_lds_floats(false)];
+  __shared__ EpiRow epr[64];
+  if (blockIdx.z == 0) gemm_pipe_body<5, NT0, 0, true>(a0, lds, epr);
+  else gemm_pipe_body<5, NT1, 0, true>(a1, lds, epr);
+}
+
 void launch_pipe(const GemmArgs& a, int ma, int mb, int batch, hipStream_t st);
+void launch_pipe_pair(const GemmArgs& a0, const GemmArgs& a1, hipStream_t st);   // gemm_f32_pipe_pair.hip
 
 }  // namespace a2m

@@ -798,20 +798,26 @@ int a2m_convt1d_tap_fwd_f32(const float* x, int64_t xs_b, int64_t xs_c, int32_t 
   // shifts off0 - nt + 1 .. off0 (a2m_convt1d_tap_pack_f32's reversed tap order), written to
   // y[.., s*u + r]: the same phase decomposition as a2m_convt1d_packed_fwd_f32, with each
   // chunk's x window loaded once for all of the phase's taps instead of gathered per tap.
+  // The two phases of a stride-2 layer are independent (the same x, disjoint output columns):
+  // where both have taps and the engine takes them, they go out as one paired launch at one
+  // split each (gemm_pair; a2m_convt_pair_override), otherwise one gemm() per phase.
   hipStream_t st = as_stream(stream);
   size_t off = 0;
-  for (int r = 0; r < stride; ++r) {
+  struct Phase {
+    Gather A, B;
+    Epilogue E;
+    int K;   // taps * Ci; 0: the phase only gets the bias / BN / act of zero
+  };
+  auto describe = [&](int r, Phase& p) -> int {
     int kk0 = -1, ntap = 0;
     for (int kk = 0; kk < ks; ++kk)
       if ((((r + pad - kk) % stride) + stride) % stride == 0) { if (kk0 < 0) kk0 = kk; ++ntap; }
-    float* yr = y + r;
-    Epilogue E = epi_bn(yr, bias, bn_w, bn_b, bn_rm, bn_rv, bn_eps, act, slope);
-    E.N1 = 1; E.N2 = Tin; E.so0 = (int)ys_b; E.so1 = 0; E.so2 = stride; E.som = (int)ys_c;
-    if (ntap == 0) {  // this phase only gets the bias / BN / act of zero
-      int rc = gemm(dense_rk(packed, 1), dense_rk(x, 1), E, Co, B * Tin, 0, 1, nullptr, 0, st);
-      if (rc) return rc;
-      continue;
-    }
+    p.E = epi_bn(y + r, bias, bn_w, bn_b, bn_rm, bn_rv, bn_eps, act, slope);
+    p.E.N1 = 1; p.E.N2 = Tin; p.E.so0 = (int)ys_b; p.E.so1 = 0; p.E.so2 = stride; p.E.som = (int)ys_c;
+    p.K = ntap * Ci;
+    p.A = dense_rk(ntap ? packed + off : packed, ntap ? ntap * Ci : 1);
+    p.B = dense_rk(x, 1);
+    if (ntap == 0) return A2M_OK;
     const int cw = (r + pad - kk0) / stride - ntap + 1;
     A2M_CHECK_ARG(cw > -Tin && cw + ntap - 1 < Tin, "convt1d_tap: tap shift %d..%d outside the clip",
                   cw, cw + ntap - 1);
@@ -820,9 +826,30 @@ int a2m_convt1d_tap_fwd_f32(const float* x, int64_t xs_b, int64_t xs_c, int32_t 
     Bg.sr0 = (int)xs_b; Bg.R1 = 1; Bg.R2 = Tin; Bg.sk0 = (int)xs_c;
     Bg.K1 = Bg.K2 = 1; Bg.divh = Bg.divw = 1; Bg.Lh = Bg.Lw = 1;
     Bg.cw = cw; Bg.tapconv = ntap;
-    int rc = gemm(dense_rk(packed + off, ntap * Ci), Bg, E, Co, B * Tin, ntap * Ci, 1, ws, ws_bytes, st);
-    if (rc) return rc;
+    p.B = Bg;
     off += (size_t)Co * ntap * Ci;
+    return A2M_OK;
+  };
+  auto run = [&](const Phase& p) {
+    return gemm(p.A, p.B, p.E, Co, B * Tin, p.K, 1, p.K ? ws : nullptr, p.K ? ws_bytes : 0, st);
+  };
+  if (stride == 2) {
+    Phase p0, p1;
+    int rc = describe(0, p0);
+    if (rc == A2M_OK) rc = describe(1, p1);
+    if (rc) return rc;
+    if (p0.K > 0 && p1.K > 0) {
+      rc = gemm_pair(p0.A, p0.B, p0.E, p0.K, p1.A, p1.B, p1.E, p1.K, Co, B * Tin, st);
+      if (rc != kGemmPairNotTaken) return rc;
+    }
+    rc = run(p0);
+    return rc ? rc : run(p1);
+  }
+  for (int r = 0; r < stride; ++r) {
+    Phase p;
+    int rc = describe(r, p);
+    if (rc == A2M_OK) rc = run(p);
+    if (rc) return rc;
   }
   return A2M_OK;
 }

@@ -609,6 +609,12 @@ int a2m_gemm_plan_override(int32_t tile, int32_t splits);
  * tile (gemm_pipe.h / gemm_pipe_bf16.h), 0 gemm_tile, -1 the default
  * (1).  Both give bitwise-equal results; process-global, not for production. */
 int a2m_gemm_pipe_override(int32_t mode);
+/* Test / tuning hook: whether a2m_convt1d_tap_fwd_f32 issues the two output phases of a stride-2
+ * layer as one paired launch of the fp32 pipelined tile (each phase at one split) -- 1 wherever
+ * the engine can take both phases, 0 never (one launch per phase, as every other geometry), -1 the
+ * default: as 1, but only where the pair puts at least one 64x64 tile on every CU.  Each phase's
+ * result is bitwise that of its own launch at one split; process-global, not for production. */
+int a2m_convt_pair_override(int32_t mode);
 /* Test hook: V channels per workgroup of the fused eval SelfAttention at C % 128 == 0 -- 64
  * (default: eight waves, Q / K computed by each of the C / 64 chunks) or 128 (twelve waves, Q / K
  * once per two 64-channel chunks: less kernel time, but measured 0.5-0.7 % slower a step).  Both
