@@ -131,6 +131,10 @@ SIGNATURES = {
     'a2m_gather_segments_f32': (ctypes.c_int, [P, P, P, I32, P, P]),
     'a2m_gemm_f32': (ctypes.c_int, [I32, I32, I32, I32, I32, I32, P, I64, I64, I64, I64, P, I64, I64, I64,
                                     I64, I64, P, I64, I64, I64, I64, P, F32, I32, P, SZ, P]),
+    'a2m_gemm_f32_route': (ctypes.c_int, [I32, I32, I32, I32, I32, I32, P, I64, I64, I64, I64, P, I64, I64,
+                                          I64, I64, I64, P, I64, I64, I64, I64, P, F32, I32,
+                                          ctypes.POINTER(I32)]),
+    'a2m_gemm_kernel_counts': (ctypes.c_int, [ctypes.POINTER(I64), I32]),
     'a2m_pose_moments_f32': (ctypes.c_int, [P, I64, I32, P, P]),
     'a2m_pose_normalize_f32': (ctypes.c_int, [P, I64, P, P, P, P]),
     'a2m_pose_denormalize_f32': (ctypes.c_int, [P, I64, P, P, P, P]),

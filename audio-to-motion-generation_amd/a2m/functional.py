@@ -1090,6 +1090,17 @@ class gemm_timing:
         return False
 
 
+GEMM_KIND_TILE, GEMM_KIND_TILE_KS2, GEMM_KIND_PIPE, GEMM_KIND_PIPE_PAIR = range(4)   # A2M_GEMM_KIND_*
+
+
+def gemm_kernel_counts(reset=False):
+    """Engine launches per kind ([GEMM_KIND_*]) since the last reset (a2m_gemm_kernel_counts)."""
+    import ctypes
+    c = (ctypes.c_int64 * 4)()
+    N.check(N.lib.a2m_gemm_kernel_counts(c, int(reset)))
+    return list(c)
+
+
 def timing_mark_to_launch_end(slot, rec):
     """ms from mark `slot` to the last block end of engine launch record `rec` (its tile kernel
     or split-K reduce) in the latest execution of the kept timing window (no re-arm)."""

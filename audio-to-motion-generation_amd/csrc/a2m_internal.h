@@ -5,6 +5,7 @@
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>
+#include <cstdlib>
 #include <string>
 
 #include "../../include/a2m.h"
@@ -42,6 +43,11 @@ void set_error(const char* fmt, ...);
 inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
 
 inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
+
+inline int env_int(const char* name, int dflt) {
+  const char* v = std::getenv(name);
+  return v ? std::atoi(v) : dflt;
+}
 
 // ---------------------------------------------------------------------------------------
 // Implicit-GEMM operand description.  Element (r, k) of an operand viewed as [R][K]:
@@ -133,6 +139,11 @@ size_t gemm_ws_bytes(int M, int N, int K, int batch);
 constexpr int kGemmPairNotTaken = 1;
 int gemm_pair(const Gather& A0, const Gather& B0, const Epilogue& E0, int K0, const Gather& A1,
               const Gather& B1, const Epilogue& E1, int K1, int M, int N, hipStream_t stream);
+// Per-launch timing records of the engine (gemm_timing.hip; a2m_gemm_timing_*).  timing_open
+// returns the launch's span-stamp slots (GemmArgs::ts), or null when timing is off or the window
+// is full; `reduce`: the launch has a split-K reduce kernel whose spans are read too.
+bool timing_enabled();
+unsigned long long* timing_open(double flops, const char* desc, bool reduce, hipStream_t stream);
 
 // shared host-side launch helpers (defined next to their kernels)
 int softmax_rows(float* x, int rows, int n, hipStream_t st);                       // ops.hip

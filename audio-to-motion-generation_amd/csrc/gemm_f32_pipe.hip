@@ -5,22 +5,16 @@
 __device__ unsigned long long g_pipe_stamps[kPipeStampBlocks * 6];
 #endif
 namespace a2m {
-void launch_pipe(const GemmArgs& a, int ma, int mb, int batch, hipStream_t st) {
+bool launch_pipe(const GemmArgs& a, int mb, int nt, int ma, int batch, hipStream_t st) {
   const dim3 grid((unsigned)cdiv(a.N, 64), (unsigned)cdiv(a.M, 64), (unsigned)(batch * a.splits));
-  if (mb == 4) { hipLaunchKernelGGL((gemm_pipe_kernel<4, 0, 4>), grid, dim3(256), 0, st, a); return; }
-  if (mb == 1) { hipLaunchKernelGGL((gemm_pipe_kernel<7, 0, 4>), grid, dim3(256), 0, st, a); return; }   // stride-2 runs
-  if (ma == 3) {
-    if (mb == 3) hipLaunchKernelGGL((gemm_pipe_kernel<3, 0, 3>), grid, dim3(256), 0, st, a);
-    else hipLaunchKernelGGL((gemm_pipe_kernel<0, 0, 3>), grid, dim3(256), 0, st, a);
-    return;
+#define A2M_PIPE_LAUNCH(MB, NT, MA)                                                      \
+  if (mb == MB && nt == NT && ma == MA) {                                                \
+    hipLaunchKernelGGL((gemm_pipe_kernel<MB, NT, MA>), grid, dim3(256), 0, st, a);       \
+    return true;                                                                         \
   }
-  if (mb == 5 && a.B.halo) hipLaunchKernelGGL((gemm_pipe_kernel<5, 0>), grid, dim3(256), 0, st, a);
-  else if (mb == 5 && a.B.tapconv == 1) hipLaunchKernelGGL((gemm_pipe_kernel<5, 1>), grid, dim3(256), 0, st, a);
-  else if (mb == 5 && a.B.tapconv == 2) hipLaunchKernelGGL((gemm_pipe_kernel<5, 2>), grid, dim3(256), 0, st, a);
-  else if (mb == 5) hipLaunchKernelGGL((gemm_pipe_kernel<5, 3>), grid, dim3(256), 0, st, a);
-  else if (mb == 6) hipLaunchKernelGGL(gemm_pipe_kernel<6>, grid, dim3(256), 0, st, a);
-  else if (mb == 3) hipLaunchKernelGGL(gemm_pipe_kernel<3>, grid, dim3(256), 0, st, a);
-  else hipLaunchKernelGGL(gemm_pipe_kernel<0>, grid, dim3(256), 0, st, a);
+  A2M_PIPE_VARIANTS(A2M_PIPE_LAUNCH)
+#undef A2M_PIPE_LAUNCH
+  return false;
 }
 }  // namespace a2m
 

@@ -726,7 +726,16 @@ __global__ __launch_bounds__(256) void gemm_pipe_kernel_pair(GemmArgs a0, GemmAr
   else gemm_pipe_body<5, NT1, 0, true>(a1, lds, epr);
 }
 
-void launch_pipe(const GemmArgs& a, int ma, int mb, int batch, hipStream_t st);
-void launch_pipe_pair(const GemmArgs& a0, const GemmArgs& a1, hipStream_t st);   // gemm_f32_pipe_pair.hip
+// Every <MB, NT, MA> the pipelined tiles (this one and gemm_pipe_bf16.h's) are instantiated at: the
+// mode-4 weight gradients (B in runs, or stride-2 runs as MB 7), plain [K][M] A with mode-3 or
+// dense B, mode 5 in the halo layout (NT 0) and per tap (NT = taps), channels-last rows, plain
+// mode-3 rows, dense rows.  gemm_route() (gemm_route.cpp) names one of them per launch.
+#define A2M_PIPE_VARIANTS(X) \
+  X(4, 0, 4) X(7, 0, 4) X(3, 0, 3) X(0, 0, 3) X(5, 0, 0) X(5, 1, 0) X(5, 2, 0) X(5, 3, 0) X(6, 0, 0) X(3, 0, 0) X(0, 0, 0)
+
+// launch of variant <mb, nt, ma>; false: no such variant
+bool launch_pipe(const GemmArgs& a, int mb, int nt, int ma, int batch, hipStream_t st);
+// gemm_f32_pipe_pair.hip: per-tap problems of nt0 and nt1 taps (1-3 each)
+void launch_pipe_pair(const GemmArgs& a0, const GemmArgs& a1, int nt0, int nt1, hipStream_t st);
 
 }  // namespace a2m

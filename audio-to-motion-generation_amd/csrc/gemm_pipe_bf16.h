@@ -594,6 +594,7 @@ __global__ __launch_bounds__(256) void gemm_pipe_bf16_kernel(GemmArgs args) {
   span_end(args.ts);
 }
 
-void launch_pipe_bf16(const GemmArgs& a, int ma, int mb, int batch, hipStream_t st);
+// launch of variant <mb, nt, ma> of A2M_PIPE_VARIANTS (gemm_pipe.h); false: no such variant
+bool launch_pipe_bf16(const GemmArgs& a, int mb, int nt, int ma, int batch, hipStream_t st);
 
 }  // namespace a2m

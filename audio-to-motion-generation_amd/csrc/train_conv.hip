@@ -12,6 +12,7 @@
 #include <cstdlib>
 
 #include "a2m_internal.h"
+#include "gemm_route.h"
 
 namespace a2m {
 
@@ -223,12 +224,16 @@ int a2m_conv2d_wgrad_f32(const float* dy, int32_t B, int32_t Co, int32_t Ho, int
   return gemm(A, Bg, E, Co, Ci * kh * kw, B * Ho * Wk, 1, ws, ws_bytes, as_stream(stream));
 }
 
-int a2m_gemm_f32(int32_t M, int32_t N, int32_t N1, int32_t K, int32_t K1, int32_t batch,
-                 const float* A, int64_t a_bs, int64_t a_m, int64_t a_k0, int64_t a_k1,
-                 const float* B, int64_t b_bs, int64_t b_n0, int64_t b_n1, int64_t b_k0,
-                 int64_t b_k1, float* C, int64_t c_bs, int64_t c_m, int64_t c_n0, int64_t c_n1,
-                 const float* bias, float alpha, int32_t accumulate, void* ws, size_t ws_bytes,
-                 void* stream) {
+// the operands and epilogue of a2m_gemm_f32 / a2m_gemm_f32_route (checked there, or A2M_EINVAL)
+struct GemmF32Problem {
+  a2m::Gather A, B;
+  a2m::Epilogue E;
+};
+static int gemm_f32_problem(GemmF32Problem& p, int32_t M, int32_t N, int32_t N1, int32_t K, int32_t K1, int32_t batch,
+                            const float* A, int64_t a_bs, int64_t a_m, int64_t a_k0, int64_t a_k1,
+                            const float* B, int64_t b_bs, int64_t b_n0, int64_t b_n1, int64_t b_k0,
+                            int64_t b_k1, float* C, int64_t c_bs, int64_t c_m, int64_t c_n0, int64_t c_n1,
+                            const float* bias, float alpha, int32_t accumulate) {
   A2M_CHECK_ARG(A && B && C && M > 0 && N > 0 && K >= 0 && batch > 0 && N1 > 0 && K1 > 0 &&
                     N % N1 == 0 && K % K1 == 0, "gemm: bad args");
   A2M_CHECK_ARG(alpha == 1.f, "gemm: only alpha = 1 is supported");
@@ -250,7 +255,38 @@ int a2m_gemm_f32(int32_t M, int32_t N, int32_t N1, int32_t K, int32_t K1, int32_
   Epilogue E = epi_dense(C, 0, c_bs);
   E.N1 = 1; E.N2 = N1; E.so0 = (int)c_n0; E.so2 = (int)c_n1; E.som = (int)c_m;
   E.bias = bias; E.accumulate = accumulate;
-  return gemm(Ag, Bg, E, M, N, K, batch, ws, ws_bytes, as_stream(stream));
+  p.A = Ag; p.B = Bg; p.E = E;
+  return A2M_OK;
+}
+
+int a2m_gemm_f32(int32_t M, int32_t N, int32_t N1, int32_t K, int32_t K1, int32_t batch,
+                 const float* A, int64_t a_bs, int64_t a_m, int64_t a_k0, int64_t a_k1,
+                 const float* B, int64_t b_bs, int64_t b_n0, int64_t b_n1, int64_t b_k0,
+                 int64_t b_k1, float* C, int64_t c_bs, int64_t c_m, int64_t c_n0, int64_t c_n1,
+                 const float* bias, float alpha, int32_t accumulate, void* ws, size_t ws_bytes,
+                 void* stream) {
+  GemmF32Problem p;
+  const int rc = gemm_f32_problem(p, M, N, N1, K, K1, batch, A, a_bs, a_m, a_k0, a_k1, B, b_bs, b_n0, b_n1, b_k0,
+                                  b_k1, C, c_bs, c_m, c_n0, c_n1, bias, alpha, accumulate);
+  if (rc != A2M_OK) return rc;
+  return gemm(p.A, p.B, p.E, M, N, K, batch, ws, ws_bytes, as_stream(stream));
+}
+
+int a2m_gemm_f32_route(int32_t M, int32_t N, int32_t N1, int32_t K, int32_t K1, int32_t batch,
+                       const float* A, int64_t a_bs, int64_t a_m, int64_t a_k0, int64_t a_k1,
+                       const float* B, int64_t b_bs, int64_t b_n0, int64_t b_n1, int64_t b_k0,
+                       int64_t b_k1, float* C, int64_t c_bs, int64_t c_m, int64_t c_n0, int64_t c_n1,
+                       const float* bias, float alpha, int32_t accumulate, int32_t out[8]) {
+  A2M_CHECK_ARG(out != nullptr, "gemm_route: null out");
+  GemmF32Problem p;
+  const int rc = gemm_f32_problem(p, M, N, N1, K, K1, batch, A, a_bs, a_m, a_k0, a_k1, B, b_bs, b_n0, b_n1, b_k0,
+                                  b_k1, C, c_bs, c_m, c_n0, c_n1, bias, alpha, accumulate);
+  if (rc != A2M_OK) return rc;
+  const a2m::GemmRoute r = a2m::gemm_route(p.A, p.B, p.E, M, N, K, batch, 0, a2m::route_config());
+  const int32_t o[8] = {r.kind, r.tile, r.bk, r.splits, r.kchunk, r.ma, r.mb,
+                        (r.vec4 ? 1 : 0) | (r.mcontig ? 2 : 0) | (r.halo ? 4 : 0) | (r.reduce ? 8 : 0)};
+  for (int i = 0; i < 8; ++i) out[i] = o[i];
+  return A2M_OK;
 }
 
 }  // extern "C"

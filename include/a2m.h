@@ -546,6 +546,27 @@ int a2m_gemm_f32(int32_t M, int32_t N, int32_t N1, int32_t K, int32_t K1, int32_
                  const float* bias, float alpha, int32_t accumulate, void* ws, size_t ws_bytes,
                  void* stream);
 
+/* Which tile kernel an engine launch runs: gemm_tile with one wave group per 64x64 / 128x128 tile,
+ * gemm_tile with two wave groups (fp32 dense 64x64), the software-pipelined 64x64 tile (fp32 or
+ * bf16 operands), or the paired launch of two ConvTranspose1d phases on the pipelined tile. */
+#define A2M_GEMM_KIND_TILE 0
+#define A2M_GEMM_KIND_TILE_KS2 1
+#define A2M_GEMM_KIND_PIPE 2
+#define A2M_GEMM_KIND_PIPE_PAIR 3
+/* The launch decision a2m_gemm_f32 would take for these arguments under the current precision
+ * and overrides, without launching: out = {kind (A2M_GEMM_KIND_*), tile, k-tile depth, split-K
+ * count, k per split, A operand mode, B operand mode, flags}; flags bit 0: float4 output rows,
+ * bit 1: m-contiguous output, bit 2: halo layout, bit 3: a split-K reduce kernel follows.
+ * The pointers are inspected for alignment only and never dereferenced; no GPU is needed. */
+int a2m_gemm_f32_route(int32_t M, int32_t N, int32_t N1, int32_t K, int32_t K1, int32_t batch,
+                       const float* A, int64_t a_bs, int64_t a_m, int64_t a_k0, int64_t a_k1,
+                       const float* B, int64_t b_bs, int64_t b_n0, int64_t b_n1, int64_t b_k0,
+                       int64_t b_k1, float* C, int64_t c_bs, int64_t c_m, int64_t c_n0, int64_t c_n1,
+                       const float* bias, float alpha, int32_t accumulate, int32_t out[8]);
+/* Engine launches per kind (counts[A2M_GEMM_KIND_*]) since the last reset; a paired launch counts
+ * once, a launch captured into a graph counts at capture.  reset != 0 zeroes the counters. */
+int a2m_gemm_kernel_counts(int64_t counts[4], int32_t reset);
+
 /* torch.optim.Adam step (no weight decay by default, no amsgrad) over a flat buffer. */
 int a2m_adam_f32(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n,
                  float lr, float beta1, float beta2, float eps, float weight_decay, int32_t step,

@@ -105,9 +105,11 @@ def test_pair_bitwise_equals_sequential_and_matches_torch(eng, name):
     _, N = eng
     run, ref = _runner(name)
     N.check(N.lib.a2m_convt_pair_override(1))
+    F.gemm_kernel_counts(reset=True)
     with F.gemm_timing() as t:
         run()
     assert t.launches == 1, f'{name}: the pair was not taken ({t.launches} launches)'
+    assert F.gemm_kernel_counts() == [0, 0, 0, 1]   # one GEMM_KIND_PIPE_PAIR launch, nothing else
     pair, seq = _both(N, run)
     assert pair.shape == ref.shape
     e_pair, e_seq = rel_err(pair.cpu(), ref), rel_err(seq.cpu(), ref)
@@ -126,9 +128,12 @@ def test_stride4_keeps_sequential_path(eng):
     xd, wd, bd = x.to(DEV), w.to(DEV), b.to(DEV)
     cache = {}
     N.check(N.lib.a2m_convt_pair_override(1))
+    F.gemm_kernel_counts(reset=True)
     with F.gemm_timing() as t:
         F.convt1d(xd, wd, bd, 4, 1, 0, cache=cache)
     assert t.launches == 4
+    counts = F.gemm_kernel_counts()
+    assert counts[F.GEMM_KIND_PIPE_PAIR] == 0 and sum(counts) == 4
     on, off = _both(N, lambda: F.convt1d(xd, wd, bd, 4, 1, 0, cache=cache), off_split=0)
     assert torch.equal(on, off) and rel_err(on.cpu(), ref) < TOL
 
@@ -143,9 +148,12 @@ def test_bf16_keeps_sequential_path(eng):
     a2m.set_gemm_precision('bf16')
     cache = {}
     N.check(N.lib.a2m_convt_pair_override(1))
+    F.gemm_kernel_counts(reset=True)
     with F.gemm_timing() as t:
         F.convt1d(xd, wd, bd, cache=cache)
     assert t.launches == 2
+    counts = F.gemm_kernel_counts()
+    assert counts[F.GEMM_KIND_PIPE_PAIR] == 0 and sum(counts) == 2
     on, off = _both(N, lambda: F.convt1d(xd, wd, bd, cache=cache), off_split=0)
     assert torch.equal(on, off) and rel_err(on.cpu(), ref) < 2e-2   # bf16 operands (tests/test_gpu_pipe.py)
 
@@ -158,9 +166,11 @@ def test_default_rule_pairs_only_launches_that_fill_the_chip(eng):
     for (B, Ci, Co, T), paired in (((64, 64, 512, 16), True), ((64, 64, 448, 16), False)):   # 2 x 128 / 2 x 112 tiles
         xd, wd = _rand(B, Ci, T, seed=57).to(DEV), _rand(Ci, Co, 3, seed=58, scale=0.1).to(DEV)
         cache = {}
+        F.gemm_kernel_counts(reset=True)
         with F.gemm_timing() as t:
             y = F.convt1d(xd, wd, None, cache=cache)
         assert (t.launches == 1) == paired, (Co, t.launches)
+        assert F.gemm_kernel_counts()[F.GEMM_KIND_PIPE_PAIR] == (1 if paired else 0)
         N.check(N.lib.a2m_convt_pair_override(0))
         N.check(N.lib.a2m_gemm_plan_override(64, 1))
         try:
@@ -203,8 +213,10 @@ def test_pair_timing_is_one_record_with_both_phases_flops(eng):
         run, _ = _runner(name)
         N.check(N.lib.a2m_convt_pair_override(1))
         run()   # packs the weights outside the window
+        F.gemm_kernel_counts(reset=True)
         with F.gemm_timing() as t:
             run()
         assert t.launches == 1 and t.reduces == 0 and t.ms_reduce == 0
+        assert F.gemm_kernel_counts() == [0, 0, 0, 1]
         assert t.flops == 2.0 * Co * B * Tin * ks * Ci
         assert t.ms_tile > 0

@@ -8,9 +8,20 @@ and ConvTranspose phases (mode 5, two taps with a shift), channels-last conv row
 Both tiles compute the same products in the same order, so the results are bitwise equal, except
 fp32 dense rows, whose gemm_tile path is the two-wave-group tile (KS = 2: the k halves summed in a
 different order, fp32 rounding apart).  a2m_gemm_pipe_override switches the tile per call.
+
+Which tile ran is read from the engine's launch counters (a2m_gemm_kernel_counts), so a case that
+fell back to gemm_tile under override 1 would fail rather than compare gemm_tile with itself.  The
+expected kinds are those of the commit before the route refactor: its A2M_GEMM_LOG=1 lines for
+every (case, prec, split, override), tests/golden/gemm_pipe_parent_log.txt, each run under a
+'# case=... prec=... split=... pipe=...' marker line.
 """
+import collections
+import os
+
 import pytest
 import torch
+
+from conftest import GOLDEN
 
 pytestmark = pytest.mark.gpu
 DEV = 'cuda'
@@ -152,6 +163,24 @@ CASES = {
 }
 
 
+def _parent_kinds():
+    """(case, prec, split, pipe override) -> [launches on the pipelined tile, on gemm_tile, paired]."""
+    kinds, key = collections.defaultdict(lambda: [0, 0, 0]), None
+    with open(os.path.join(GOLDEN, 'gemm_pipe_parent_log.txt')) as f:
+        for line in f:
+            if line.startswith('# '):
+                c = dict(kv.split('=') for kv in line[2:].split())
+                key = (c['case'], c['prec'], int(c['split']), int(c['pipe']))
+            elif line.startswith('a2m gemm pair '):
+                kinds[key][2] += 1
+            elif line.startswith('a2m gemm '):
+                kinds[key][0 if '(pipe)' in line else 1] += 1
+    return dict(kinds)
+
+
+PARENT_KINDS = _parent_kinds()
+
+
 @pytest.mark.parametrize('prec', ['fp32', 'bf16'])
 @pytest.mark.parametrize('split', [0, 3])
 @pytest.mark.parametrize('case', sorted(CASES))
@@ -159,11 +188,19 @@ def test_pipe_tile_matches_gemm_tile(eng, prec, split, case):
     a2m, N = eng
     a2m.set_gemm_precision(prec)
     N.check(N.lib.a2m_gemm_plan_override(64, split))
+    from a2m import functional as F
     run, ref, dense_rows = CASES[case]()
     outs = []
     for mode in (1, 0):
         N.check(N.lib.a2m_gemm_pipe_override(mode))
+        F.gemm_kernel_counts(reset=True)
         outs.append(run().clone())
+        tile, ks2, pipe, pair = F.gemm_kernel_counts(reset=True)
+        assert [pipe, tile + ks2, pair] == PARENT_KINDS[case, prec, split, mode], (case, prec, split, mode)
+        if mode == 0:
+            assert pipe == 0 and pair == 0
+        else:
+            assert pipe > 0   # every case reaches the pipelined tile
     torch.cuda.synchronize()
     pipe, tile = outs
     tol = 1e-4 if prec == 'fp32' else 2e-2
