@@ -37,16 +37,22 @@ def generate(generator, audio, pose_mean=None, pose_std=None):
 
 @torch.no_grad()
 def generate_from_wave(generator, wave, sr, starts=None, time=4.3, fs_new=15, audio_mean=None,
-                       audio_std=None, pose_mean=None, pose_std=None, **mel_kwargs):
+                       audio_std=None, pose_mean=None, pose_std=None, resample_to=None,
+                       res_type='kaiser_best', **mel_kwargs):
     """A recording to poses in one call: wave [S] (device) -> audio/log_mel_512 windows as the
     PATS loader cuts them (windowing.window_index: `time` seconds at 89 feature frames/s read
     every round(89 / fs_new)-th frame, i.e. 382 / 6 -> T = 64; only those frames are computed),
     standardised with audio_mean / audio_std when given -> generator -> poses [n, T, 104],
     de-normalised when pose_mean / pose_std are given.  `starts` (feature-frame index of each
     window) defaults to the loader's non-overlapping windows; mel_kwargs go to
-    pats_audio.log_mel_512_windows (eps, pad_mode)."""
-    from .pats_audio import log_mel_512_windows, num_frames
+    pats_audio.log_mel_512_windows (eps, pad_mode).  The windows assume the rate the PATS features
+    were made at (89 frames/s x hop 512); a recording at another rate is brought there on the
+    device with resample_to=<that rate> (pats_audio.resample, filter `res_type`), and everything
+    downstream then takes resample_to as the rate.  None: the wave is used as it is."""
+    from .pats_audio import log_mel_512_windows, num_frames, resample
     from .windowing import window_index
+    if resample_to is not None:
+        wave, sr = resample(wave, sr, resample_to, res_type), resample_to
     auto, window, interval = window_index(num_frames(wave.shape[-1], 2048, 512, True),
                                           'audio/log_mel_512', fs_new, time)
     audio = log_mel_512_windows(wave, sr, auto if starts is None else starts, window, interval,

@@ -8,8 +8,15 @@
   log_mel_400(y, sr=16000, eps=1e-6, out=None)
       n_fft 512, hop 160, a 400-sample Hann centred in the frame, no padding, magnitude
       spectrum, 64 Slaney mels 125..7500 Hz without normalisation; frames = 1 + (S - 512) // 160.
-      The reference resamples to 16 kHz first; resampling is not implemented, so any other
-      sr raises ValueError.
+      Works on 16 kHz audio only: any other sr raises ValueError (log_mel_400_resampled is the
+      entry that resamples first, as the reference does).
+  resample(y, orig_sr, target_sr, res_type='kaiser_best', out=None)
+      librosa.core.resample as the reference calls it (audio.py:88): band-limited interpolation
+      with a Kaiser-windowed sinc, resampy's 'kaiser_best' (64 zero crossings) or 'kaiser_fast'
+      (16) parameters, the continuous filter evaluated exactly; ceil(S * target_sr / orig_sr)
+      samples.  Equal rates return y itself.
+  log_mel_400_resampled(y, sr, eps=1e-6, res_type='kaiser_best')
+      == log_mel_400(resample(y, sr, 16000)): the reference's audio/log_mel_400 (audio.py:86-120).
   log_mel_512_windows(wave, sr, starts, window=382, interval=6, mean=None, std=None, ...)
       == gather_windows(log_mel_512(wave, sr), starts, window, interval, mean, std), computing
       only the frames the gather reads (every `interval`-th of each window).
@@ -17,7 +24,8 @@
 `y` may be a 1-D numpy array (returns numpy [F, M], as the reference does) or a device tensor
 [S] / [C, S] with contiguous samples (rows may be strided; returns [F, M] / [C, F, M]).
 Computation and output are fp32 on the GPU (reference: float64 numpy); DESIGN.md section 4, PATS
-audio features, has the semantics and the numbers.  There is no CPU path.
+audio features, has the semantics and the numbers.  There is no CPU path.  resample takes and
+returns the same forms ([S] numpy -> numpy; [S] / [C, S] device -> [S'] / [C, S']).
 """
 import ctypes
 
@@ -131,6 +139,94 @@ def log_mel_512(y, sr, eps=1e-10, pad_mode='reflect', n_mels=128, out=None):
 
 def log_mel_400(y, sr=16000, eps=1e-6, out=None):
     return _feature(y, _cfg_400(sr), False, 'constant', eps, out)
+
+
+# ------------------------------------------------------------------------------ resampling
+# res_type -> (zero crossings, Kaiser beta, roll-off): resampy's published filter designs
+RES_TYPES = {'kaiser_best': (64, 14.769656459379492, 0.9475937167399596),
+             'kaiser_fast': (16, 8.555504641634386, 0.85)}
+
+
+class ResamplePlan:
+    """Device-resident tap bank of one (orig_sr, target_sr, filter) configuration."""
+    _cache = {}
+
+    def __init__(self, sr_in, sr_out, num_zeros, beta, rolloff, device=None):
+        self.sr_in, self.sr_out, self.num_zeros = sr_in, sr_out, num_zeros
+        args = (sr_in, sr_out, num_zeros, beta, rolloff)
+        nbytes = N.lib.a2m_resample_plan_bytes(*args)
+        self.host = torch.zeros(max(nbytes, 64), dtype=torch.uint8)
+        N.check(N.lib.a2m_resample_plan_build(*args, ctypes.c_void_p(self.host.data_ptr()),
+                                              self.host.numel()), value_error=True)
+        self.dev = self.host.to(device) if device is not None else None
+
+    @classmethod
+    def get(cls, device, *cfg):
+        key = cfg + (str(torch.device(device)),)
+        if key not in cls._cache:
+            cls._cache[key] = cls(*cfg, device=device)
+        return cls._cache[key]
+
+    def bank(self):
+        """(P, Q, L, taps): the reduced ratio, the half width and the dense float32 bank [Q, 2L],
+        row p holding h_p[k] for k = -L+1 .. L."""
+        P, Q, L = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int32()
+        hp, nb = ctypes.c_void_p(self.host.data_ptr()), self.host.numel()
+        N.check(N.lib.a2m_resample_plan_bank(hp, nb, ctypes.byref(P), ctypes.byref(Q), ctypes.byref(L), None))
+        taps = np.zeros((Q.value, 2 * L.value), np.float32)
+        N.check(N.lib.a2m_resample_plan_bank(hp, nb, None, None, None, taps.ctypes.data))
+        return P.value, Q.value, L.value, taps
+
+
+def _rate(name, v):
+    if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or v != int(v) \
+            or not 1 <= int(v) < 2 ** 31:
+        raise ValueError(f'{name} must be a positive integer sample rate, got {v!r}')
+    return int(v)
+
+
+def _resample_cfg(orig_sr, target_sr, res_type):
+    if res_type not in RES_TYPES:
+        raise ValueError(f'res_type must be one of {sorted(RES_TYPES)}, got {res_type!r}')
+    return (_rate('orig_sr', orig_sr), _rate('target_sr', target_sr)) + RES_TYPES[res_type]
+
+
+def resample_num_samples(n_samples, orig_sr, target_sr):
+    return int(N.lib.a2m_resample_num_samples(n_samples, orig_sr, target_sr))
+
+
+def resample(y, orig_sr, target_sr, res_type='kaiser_best', out=None):
+    cfg = _resample_cfg(orig_sr, target_sr, res_type)
+    if cfg[0] == cfg[1]:
+        return y
+    as_numpy = not torch.is_tensor(y)
+    if as_numpy:
+        y = torch.as_tensor(np.asarray(y, dtype=np.float32))
+    if y.dim() not in (1, 2):
+        raise ValueError(f'waveform must be [S] or [C, S], got {tuple(y.shape)}')
+    if N.lib.a2m_resample_plan_bytes(*cfg) == 0:
+        ResamplePlan(*cfg)   # a refused configuration raises before anything touches the GPU
+    wave = y.to('cuda') if as_numpy else y
+    F._check_dev(wave, out)
+    squeeze = wave.dim() == 1
+    w2 = wave.reshape(1, -1) if squeeze else wave
+    if w2.stride(1) != 1 and w2.shape[1] > 1:
+        w2 = w2.contiguous()
+    plan = ResamplePlan.get(w2.device, *cfg)
+    C, S = w2.shape
+    n_out = resample_num_samples(S, cfg[0], cfg[1])
+    if out is None:
+        out = torch.empty(C, n_out, device=w2.device, dtype=torch.float32)
+    else:
+        assert out.is_contiguous() and out.numel() == C * n_out
+    N.check(N.lib.a2m_resample_f32(F._p(w2), C, w2.stride(0), S, cfg[0], cfg[1], cfg[2], F._p(plan.dev),
+                                   F._p(out), n_out, n_out, F._stream()), value_error=True)
+    res = out.reshape(n_out) if squeeze else out.reshape(C, n_out)
+    return res.cpu().numpy() if as_numpy else res
+
+
+def log_mel_400_resampled(y, sr, eps=1e-6, res_type='kaiser_best'):
+    return log_mel_400(resample(y, sr, 16000, res_type), 16000, eps)
 
 
 _offsets = {}

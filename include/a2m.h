@@ -93,6 +93,39 @@ int a2m_pats_audio_f32(const float* wave, int64_t n_clips, int64_t clip_stride, 
                        const int64_t* frame_ids, int64_t n_out, const float* mean, const float* std_,
                        float* out, void* stream);
 
+/* ---------------------------------------------------------------- waveform resampling
+ * What librosa.core.resample did ahead of log_mel_400 (pats/data_loading/audio.py:88): band-limited
+ * interpolation with a Kaiser-windowed sinc of num_zeros zero crossings, Kaiser parameter beta and
+ * roll-off `rolloff` (resampy's kaiser_best: 64, 14.769656459379492, 0.9475937167399596;
+ * kaiser_fast: 16, 8.555504641634386, 0.85).  With g = gcd(sr_in, sr_out), P = sr_in/g, Q = sr_out/g,
+ * s = min(1, sr_out/sr_in), L = ceil(num_zeros / s), output t sits at input position t P / Q,
+ * n_t = (t P) div Q, p_t = (t P) mod Q in 64-bit integers, and
+ *   y[t] = sum_{k=-L+1..L} h_{p_t}[k] x[n_t + k],  x = 0 outside [0, n_samples),
+ *   h_p[k] = s rolloff sinc(s rolloff tau) w(s tau / num_zeros),  tau = (p - k Q) / Q,
+ *   w(u) = I0(beta sqrt(1 - u^2)) / I0(beta) for |u| < 1, else 0,
+ * the continuous filter evaluated exactly (no interpolated table).  Output length
+ * ceil(n_samples sr_out / sr_in).  The plan (the Q x 2L taps) is built on the HOST in float64, stored
+ * as float32 and copied to the device by the caller, like the log-mel plans.  A2M_EINVAL: a rate or
+ * num_zeros below 1, rolloff outside (0, 1], beta < 0, or a reduced ratio P/Q whose bank Q 2L
+ * exceeds 2^21 floats (nearly coprime rates). */
+int64_t a2m_resample_num_samples(int64_t n_samples, int32_t sr_in, int32_t sr_out);
+size_t a2m_resample_plan_bytes(int32_t sr_in, int32_t sr_out, int32_t num_zeros, double beta,
+                               double rolloff);
+int a2m_resample_plan_build(int32_t sr_in, int32_t sr_out, int32_t num_zeros, double beta,
+                            double rolloff, void* host_plan, size_t plan_bytes);
+/* the reduced ratio, the half width and (bank != NULL) the dense bank[Q][2L]: row p holds h_p[k],
+ * k = -L+1..L.  The layout inside the plan is the kernel's own. */
+int a2m_resample_plan_bank(const void* host_plan, size_t plan_bytes, int32_t* P, int32_t* Q, int32_t* L,
+                           float* bank);
+/* wave as for a2m_logmel_f32; out[c][t] at out + c*out_stride + t, n_out =
+ * a2m_resample_num_samples().  sr_in, sr_out and num_zeros are the plan's (the plan is device
+ * memory, so the launch takes them again, as a2m_pats_audio_f32 takes its geometry).  Never reads
+ * outside a clip's [0, n_samples).  A2M_EINVAL for null pointers, negative sizes, a wrong n_out, or
+ * n_samples * Q beyond 62 bits.  No allocation, no host synchronisation: capturable. */
+int a2m_resample_f32(const float* wave, int64_t n_clips, int64_t clip_stride, int64_t n_samples,
+                     int32_t sr_in, int32_t sr_out, int32_t num_zeros, const void* dev_plan, float* out,
+                     int64_t out_stride, int64_t n_out, void* stream);
+
 /* ---------------------------------------------------------------- convolutions
  * ConvNormRelu (model_layers.py:51-118) forward in eval mode: conv + bias, optional
  * BatchNorm (running stats; bn_w == NULL disables it), activation (A2M_ACT_*, LeakyReLU
