@@ -681,6 +681,8 @@ int a2m_bn_train_fwd_f32(const float* x, int64_t xs_b, int64_t xs_c, int32_t B, 
                          int64_t ys_b, int64_t ys_c, float* save_mean, float* save_rstd,
                          void* ws, size_t ws_bytes, void* stream) {
   A2M_CHECK_ARG(x && y && save_mean && save_rstd && B > 0 && C > 0 && L > 0, "bn_train_fwd: bad args");
+  A2M_CHECK_ARG(drop_p >= 0.f && drop_p < 1.f && drop_mode >= DROP_NONE && drop_mode <= DROP_AFTER,
+                "bn_train_fwd: bad dropout (p %g, mode %d)", (double)drop_p, drop_mode);
   const int64_t N = (int64_t)B * L;
   const int S = bn_slices(N);
   A2M_CHECK_ARG(S > 0, "batchnorm: %lld elements per channel (at most 2^31 - 1)", (long long)N);
@@ -710,6 +712,8 @@ int a2m_bn_train_bwd_f32(const float* dy, int64_t dys_b, int64_t dys_c, const fl
                          int32_t act, float slope, float* dx, float* dgamma, float* dbeta,
                          float* dbias, void* ws, size_t ws_bytes, void* stream) {
   A2M_CHECK_ARG(dy && x && dx && save_mean && save_rstd && B > 0 && C > 0 && L > 0, "bn_train_bwd: bad args");
+  A2M_CHECK_ARG(drop_p >= 0.f && drop_p < 1.f && drop_mode >= DROP_NONE && drop_mode <= DROP_AFTER,
+                "bn_train_bwd: bad dropout (p %g, mode %d)", (double)drop_p, drop_mode);
   const int64_t N = (int64_t)B * L;
   const int S = bn_slices(N);
   A2M_CHECK_ARG(S > 0, "batchnorm: %lld elements per channel (at most 2^31 - 1)", (long long)N);
@@ -806,6 +810,8 @@ int a2m_bn_sync_stats_f32(const float* x, int64_t xs_b, int64_t xs_c, int32_t B,
                           int32_t L, float drop_p, int32_t drop_mode, uint64_t seed, double* sums,
                           void* ws, size_t ws_bytes, void* stream) {
   A2M_CHECK_ARG(x && sums && B > 0 && C > 0 && L > 0, "bn_sync_stats: bad args");
+  A2M_CHECK_ARG(drop_p >= 0.f && drop_p < 1.f && drop_mode >= DROP_NONE && drop_mode <= DROP_AFTER,
+                "bn_sync_stats: bad dropout (p %g, mode %d)", (double)drop_p, drop_mode);
   const int64_t N = (int64_t)B * L;
   const int S = bn_slices(N);
   A2M_CHECK_ARG(S > 0, "batchnorm: %lld elements per channel (at most 2^31 - 1)", (long long)N);
@@ -830,6 +836,8 @@ int a2m_bn_sync_apply_f32(const float* x, int64_t xs_b, int64_t xs_c, int32_t B,
                           int64_t ys_c, float* save_mean, float* save_rstd, void* stream) {
   A2M_CHECK_ARG(x && y && sums && save_mean && save_rstd && B > 0 && C > 0 && L > 0 && n_total > 0,
                 "bn_sync_apply: bad args");
+  A2M_CHECK_ARG(drop_p >= 0.f && drop_p < 1.f && drop_mode >= DROP_NONE && drop_mode <= DROP_AFTER,
+                "bn_sync_apply: bad dropout (p %g, mode %d)", (double)drop_p, drop_mode);
   const int S = bn_slices((int64_t)B * L);
   BNArgs a{x, xs_b, xs_c, B, C, L, S, drop_p, drop_mode, seed, g_seed_off};
   hipStream_t st = as_stream(stream);
@@ -850,6 +858,8 @@ int a2m_bn_sync_bwd_stats_f32(const float* dy, int64_t dys_b, int64_t dys_c, con
                               float* dgamma, float* dbeta, void* ws, size_t ws_bytes, void* stream) {
   A2M_CHECK_ARG(dy && x && sums && save_mean && save_rstd && B > 0 && C > 0 && L > 0,
                 "bn_sync_bwd_stats: bad args");
+  A2M_CHECK_ARG(drop_p >= 0.f && drop_p < 1.f && drop_mode >= DROP_NONE && drop_mode <= DROP_AFTER,
+                "bn_sync_bwd_stats: bad dropout (p %g, mode %d)", (double)drop_p, drop_mode);
   const int64_t N = (int64_t)B * L;
   const int S = bn_slices(N);
   A2M_CHECK_ARG(S > 0, "batchnorm: %lld elements per channel (at most 2^31 - 1)", (long long)N);
@@ -879,6 +889,8 @@ int a2m_bn_sync_bwd_apply_f32(const float* dy, int64_t dys_b, int64_t dys_c, con
                               void* stream) {
   A2M_CHECK_ARG(dy && x && dx && sums && save_mean && save_rstd && B > 0 && C > 0 && L > 0 &&
                 n_total > 0, "bn_sync_bwd_apply: bad args");
+  A2M_CHECK_ARG(drop_p >= 0.f && drop_p < 1.f && drop_mode >= DROP_NONE && drop_mode <= DROP_AFTER,
+                "bn_sync_bwd_apply: bad dropout (p %g, mode %d)", (double)drop_p, drop_mode);
   const int64_t N = (int64_t)B * L;
   const int S = bn_slices(N);
   A2M_CHECK_ARG(S > 0, "batchnorm: %lld elements per channel (at most 2^31 - 1)", (long long)N);
