@@ -63,6 +63,10 @@ SIGNATURES = {
                                                P, P]),
     'a2m_graph_stack_fwd_ex_f32': (ctypes.c_int, [P, I32, I32, P, P, I32, P, P, P, P, P, P, P, P, P,
                                                   F32, P, P]),
+    'a2m_graph_stack_plan_bytes': (SZ, [I32, P, P]),
+    'a2m_graph_stack_plan_build': (ctypes.c_int, [I32, P, P, P, SZ]),
+    'a2m_graph_stack_fwd_ex2_f32': (ctypes.c_int, [P, I32, I32, P, P, I32, P, P, P, P, P, P, P, P, P,
+                                                   P, F32, P, P]),
     'a2m_to_bf16_f32': (ctypes.c_int, [P, P, I64, P]),
     'a2m_conv1d_tap_pack_f32': (ctypes.c_int, [P, I32, I32, I32, I32, P, P]),
     'a2m_conv1d_tap_fwd_f32': (ctypes.c_int, [P, I64, I64, I32, I32, I32, P, I32, P, I32, I32, I32,

@@ -550,13 +550,33 @@ def graph_weights_bf16(w0, w1, cache):
     return cache['h0'], cache['h1']
 
 
-def graph_stack(x, J, nbr_ptr, nbr_idx, layers, slope=0.2, out=None, wh=None):
-    """Fused eval stack of graph layers (a2m_graph_stack_fwd_ex_f32).  x: [F*J, 64] contiguous;
+def graph_stack_plan(J, nbr_ptr, nbr_idx):
+    """The fused stack's topology plan (a2m_graph_stack_plan_build) as a CPU uint8 tensor: the
+    degree-sorted row order, in-degrees and gather slots of one workgroup tile, from the
+    in-neighbour CSR given as CPU int32 tensors.  Build it once per skeleton, move it to the
+    device and pass it to graph_stack(plan=...).  ValueError beyond the kernels' limits."""
+    nbr_ptr, nbr_idx = [torch.as_tensor(t).to(torch.int32).contiguous() for t in (nbr_ptr, nbr_idx)]
+    assert nbr_ptr.device.type == 'cpu' and nbr_idx.device.type == 'cpu' and nbr_ptr.numel() == J + 1
+    assert nbr_idx.numel() >= int(nbr_ptr[-1])
+    host = torch.zeros(max(N.lib.a2m_graph_stack_plan_bytes(J, _p(nbr_ptr), _p(nbr_idx)), 16), dtype=torch.uint8)
+    N.check(N.lib.a2m_graph_stack_plan_build(J, _p(nbr_ptr), _p(nbr_idx), ctypes.c_void_p(host.data_ptr()),
+                                             host.numel()), value_error=True)
+    return host
+
+
+def graph_stack(x, J, nbr_ptr, nbr_idx, layers, slope=0.2, out=None, wh=None, plan=None):
+    """Fused eval stack of graph layers (a2m_graph_stack_fwd_ex2_f32).  x: [F*J, 64] contiguous;
     layers: list of (kind, w0, w1, U, bias, ln_w, ln_b) with U from graph_att_proj for GAT;
-    wh: optional per-layer (w0, w1) bf16 copies (graph_weights_bf16) for the bf16 operand mode."""
+    wh: optional per-layer (w0, w1) bf16 copies (graph_weights_bf16) for the bf16 operand mode;
+    plan: optional graph_stack_plan(J, nbr_ptr, nbr_idx) on x's device (the same result; the
+    workgroups then read their topology tables instead of rebuilding them)."""
     _check_dev(x, out)
     assert x.is_contiguous() and x.shape[1] == 64 and x.shape[0] % J == 0 and 0 < len(layers) <= 8
     F = x.shape[0] // J
+    if plan is not None:
+        _check_dev_any(plan)
+        assert plan.device == x.device and plan.dtype == torch.uint8 and plan.is_contiguous() \
+            and plan.numel() >= 128 * 12
     if out is None:
         out = torch.empty_like(x)
     n = len(layers)
@@ -564,9 +584,14 @@ def graph_stack(x, J, nbr_ptr, nbr_idx, layers, slope=0.2, out=None, wh=None):
     kinds = (ctypes.c_int32 * n)(*[L[0] for L in layers])
     hp = [None, None] if wh is None else \
         [(ctypes.c_void_p * n)(*[_p(h[i]) for h in wh]) for i in (0, 1)]
-    N.check(N.lib.a2m_graph_stack_fwd_ex_f32(_p(x), F, J, _p(nbr_ptr), _p(nbr_idx), n, kinds,
-                                             ptrs(1), ptrs(2), ptrs(3), ptrs(4), ptrs(5), ptrs(6),
-                                             hp[0], hp[1], slope, _p(out), _stream()))
+    if plan is None:
+        N.check(N.lib.a2m_graph_stack_fwd_ex_f32(_p(x), F, J, _p(nbr_ptr), _p(nbr_idx), n, kinds,
+                                                 ptrs(1), ptrs(2), ptrs(3), ptrs(4), ptrs(5), ptrs(6),
+                                                 hp[0], hp[1], slope, _p(out), _stream()))
+    else:
+        N.check(N.lib.a2m_graph_stack_fwd_ex2_f32(_p(x), F, J, _p(nbr_ptr), _p(nbr_idx), n, kinds,
+                                                  ptrs(1), ptrs(2), ptrs(3), ptrs(4), ptrs(5), ptrs(6),
+                                                  hp[0], hp[1], _p(plan), slope, _p(out), _stream()))
     return out
 
 

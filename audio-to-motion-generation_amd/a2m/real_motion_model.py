@@ -29,9 +29,16 @@ class _GraphTopology(nn.Module):
             ptr, idx = S.in_neighbour_csr(getattr(self, f'{part}_edge_index_template'), n)
             self.register_buffer(f'_{part}_nbr_ptr', ptr, persistent=False)
             self.register_buffer(f'_{part}_nbr_idx', idx, persistent=False)
+            # the fused eval stack's row order / degrees / gather slots, built once per skeleton
+            # (an older library selected with A2M_LIB for an A/B run has no plan entry points)
+            if hasattr(F.N.lib, 'a2m_graph_stack_fwd_ex2_f32') or 'A2M_LIB' not in os.environ:
+                self.register_buffer(f'_{part}_stack_plan', F.graph_stack_plan(n, ptr, idx), persistent=False)
 
     def topology(self, part):
         return getattr(self, f'_{part}_nbr_ptr'), getattr(self, f'_{part}_nbr_idx')
+
+    def stack_plan(self, part):
+        return getattr(self, f'_{part}_stack_plan', None)
 
     def _load_from_state_dict(self, state_dict, prefix, local_metadata, strict, missing_keys,
                               unexpected_keys, error_msgs):
@@ -117,7 +124,7 @@ class SelfAttention_G(_GraphTopology):
                                    lns[L].weight, lns[L].bias))
                 if bf16 and _STACK_BF16_WEIGHTS:
                     wh.append(F.graph_weights_bf16(layers[-1][1], layers[-1][2], g._Wh))
-            a = F.graph_stack(a, nj, ptr, idx, layers, out=b, wh=wh or None)
+            a = F.graph_stack(a, nj, ptr, idx, layers, out=b, wh=wh or None, plan=self.stack_plan(part))
         else:
             for L in range(5):
                 g = getattr(self, f'{part}_gcn{L + 1}')

@@ -9,6 +9,8 @@
 // aggregation read LDS only, and LayerNorm(64) is a 16-lane shuffle reduction over the
 // threads that hold one node's 64 features.  HBM traffic per layer = x in + y out
 // (2 x 256 B per node); the weights stay in L2.
+#include <cstring>
+
 #include "a2m_internal.h"
 
 namespace a2m {
@@ -27,6 +29,11 @@ constexpr int GF = 64;          // joint feature dim
 #endif
 #ifndef STACK_WG_PER_CU
 #define STACK_WG_PER_CU 3
+#endif
+// 1 (shipped): the fp32 k steps load their weight fragments through raw buffer loads and
+// aggregate in plain fma chains; 0 (diagnostic builds): flat loads and float2 accumulators
+#ifndef STACK_KSTEP
+#define STACK_KSTEP 1
 #endif
 // 1: the stack's layer products computed transposed (MFMA rows = output features, columns = the
 // wave's 32 nodes), so each lane ends a layer holding 32 of its node's 64 features and the
@@ -314,7 +321,16 @@ __global__ __launch_bounds__(256, GL_WG_PER_CU) void graph_layer_kernel(
 //    are held in registers and each gathered float4 is weighted four times, so the LDS gather
 //    traffic of a GAT layer is a quarter of the per-head loop's;
 //  * the logits x . U are computed by all 256 threads (two per node, four logits each).
+//
+// The row order, degrees and neighbour slots depend only on the skeleton, so the host builds them
+// once (a2m_graph_stack_plan_build) for one full tile of 128 / J frames: GMAXN rows of
+// STACK_PLAN_ROW bytes in sorted-row order -- node, in-degree d, then the GMAXDEG gather slots (the
+// in-neighbours' tile-local node indices in edge order, the node itself at slot d, 0 after) and
+// two bytes of padding.  Rows past the tile's fpb * J nodes carry node 0xff.  Without a plan the
+// kernel builds the same tables in LDS.
 constexpr int GMAXL = 8;
+constexpr int STACK_PLAN_ROW = 12;
+constexpr size_t STACK_PLAN_BYTES = (size_t)GMAXN * STACK_PLAN_ROW;
 struct GraphStack {
   int nlayers;
   int kind[GMAXL];
@@ -351,11 +367,68 @@ __device__ __forceinline__ void stack_mfma4(const float (&af)[4], const float4 (
 
 // edge weights of a row's DL gather slots: GAT, the edge softmax per head over the in-edges + self
 // loop (slot d0; PyG: LeakyReLU 0.2); GraphConv, 1 for the in-edges
+//
+// STACK_SOFTMAX 1 (shipped): the two lanes that hold one MFMA row (l and l + 32) split the heads
+// -- half lh computes heads 2 lh and 2 lh + 1 -- and exchange the weights with v_permlane32_swap,
+// so each lane runs half the softmaxes.  Slots past the row's own (the wave gathers up to its
+// heaviest row's count) enter as -inf, LeakyReLU is max(x, 0.2 x), exp is the hardware exp2 of
+// (s - max) log2(e) and the normalisation one v_rcp: both are 1-ulp operations and the softmax
+// weights are in [0, 1], so the stack's error against fp64 stays where it was
+// (tests/test_gpu_graph_stack_plan.py prints it).  0 (diagnostic builds): every lane computes
+// all four heads with expf and an IEEE division.
+#ifndef STACK_SOFTMAX
+#define STACK_SOFTMAX 1
+#endif
+template <int DL>
+__device__ __forceinline__ void stack_edge_softmax(const float (*al)[GMAXN], const int (&id)[GMAXDEG], int node,
+                                                   int d0, int lh, float (&wq)[GHEADS][DL]) {
+  constexpr float L2E = 1.44269504088896341f;
+  // 0 for the row's in-edges and its self loop (slot d0), -inf past them.  The empty asm keeps the
+  // compiler from hoisting the DL values out of the layer loop, where they cost the bf16 kernel
+  // registers it does not have (spills); rebuilt per layer they live only through the softmax.
+  asm volatile("" : "+v"(d0));
+  float mb[DL];
+#pragma unroll
+  for (int q = 0; q < DL; ++q) mb[q] = q <= d0 ? 0.f : -INFINITY;
+#pragma unroll
+  for (int hh = 0; hh < 2; ++hh) {
+    const float* as = &al[2 * lh + hh][0];
+    const float ad = as[GHEADS * GMAXN + node];
+    float p[DL];
+    float mx = -INFINITY;
+#pragma unroll
+    for (int q = 0; q < DL; ++q) {
+      const float sv = as[id[q]] + ad;
+      p[q] = fmaxf(sv, 0.2f * sv) + mb[q];
+      mx = fmaxf(mx, p[q]);   // slot 0 is always the row's own, so mx is finite
+    }
+    const float nm = -mx * L2E;
+    float den = 0.f;
+#pragma unroll
+    for (int q = 0; q < DL; ++q) {
+      p[q] = __builtin_amdgcn_exp2f(fmaf(p[q], L2E, nm));
+      den += p[q];
+    }
+    // den >= the maximum's term ~ 1: PyG's + 1e-16 does not change it in fp32
+    const float inv = __builtin_amdgcn_rcpf(den);
+#pragma unroll
+    for (int q = 0; q < DL; ++q) {
+      // r[0]: the lower half's value in both halves (head hh), r[1]: the upper half's (head 2 + hh)
+      const uint32_t u = __float_as_uint(p[q] * inv);
+      const auto r = __builtin_amdgcn_permlane32_swap(u, u, false, false);
+      wq[hh][q] = __uint_as_float(r[0]);
+      wq[2 + hh][q] = __uint_as_float(r[1]);
+    }
+  }
+}
+
 template <int DL, bool GAT>
 __device__ __forceinline__ void stack_edge_weights(const float (*al)[GMAXN], const int (&id)[GMAXDEG], int node,
-                                                   int d0, float (&wq)[GAT ? GHEADS : 1][DL]) {
+                                                   int d0, int lh, float (&wq)[GAT ? GHEADS : 1][DL]) {
   constexpr int NS = GAT ? GHEADS : 1;
-  if (GAT) {  // edge softmax per head over the in-edges + self loop (slot d0; PyG: LeakyReLU 0.2)
+  if constexpr (GAT && STACK_SOFTMAX) {
+    stack_edge_softmax<DL>(al, id, node, d0, lh, wq);
+  } else if (GAT) {  // edge softmax per head over the in-edges + self loop (slot d0; PyG: LeakyReLU 0.2)
     const int d = d0 + 1;
 #pragma unroll
     for (int h = 0; h < NS; ++h) {
@@ -387,10 +460,62 @@ template <int DL, bool GAT>
 __device__ __forceinline__ void stack_layer_k(const float* xs, const float (*al)[GMAXN], const int (&id)[GMAXDEG],
                                               int node, int d0, const float* W0, const float* W1, int li,
                                               int lh, floatx16 (&acc)[2]) {
-  typedef float f2 __attribute__((ext_vector_type(2)));
   constexpr int NS = GAT ? GHEADS : 1;   // aggregated segments (GraphConv: + the root term)
   float wq[NS][DL];
-  stack_edge_weights<DL, GAT>(al, id, node, d0, wq);
+  stack_edge_weights<DL, GAT>(al, id, node, d0, lh, wq);
+#if STACK_KSTEP
+  // B fragments through raw buffer loads (as gemm_pipe.h's pipe_load): one per-lane byte offset
+  // for the whole layer -- B row li at this lane half's k -- with the segment, t and step offsets
+  // in the scalar offset, so a step spends no vector instruction on weight addresses.  The
+  // descriptors cover exactly the layer's weights.
+  const uint32_t boff = (uint32_t)(li * GF + lh * 8) * 4u;
+  const __amdgpu_buffer_rsrc_t rs0 = __builtin_amdgcn_make_buffer_rsrc(
+      const_cast<float*>(W0), (short)0, (GAT ? GHEADS : 1) * GF * GF * 4, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rs1 =
+      GAT ? rs0 : __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(W1), (short)0, GF * GF * 4, 0x00020000);
+  auto load_b = [&](int st, float4 (&bw)[GHEADS][2]) {
+    const uint32_t soff = (uint32_t)((st >> 1) * 16 + (st & 1) * 4) * 4u;
+#pragma unroll
+    for (int h = 0; h < (GAT ? GHEADS : 2); ++h) {
+#pragma unroll
+      for (int t = 0; t < 2; ++t) {
+        const uint32_t so = soff + (uint32_t)((GAT ? h * GF * GF : 0) + t * 32 * GF) * 4u;
+        bw[h][t] = STACK_ABL == 4 ? make_float4(W0[0] * st, 1.f, 0.5f, (float)h)
+                                  : __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(
+                                        (GAT || h == 0) ? rs0 : rs1, boff, so, 0));
+      }
+    }
+  };
+  // the gather rows' LDS addresses at this lane half's k, once per layer
+  const float* xr[DL];
+#pragma unroll
+  for (int q = 0; q < DL; ++q) xr[q] = xs + (STACK_ABL == 2 ? node : id[q]) * ZP + lh * 8;
+  const float* xo = xs + node * ZP + lh * 8;
+  auto step = [&](int st, const float4 (&bc)[GHEADS][2]) {
+#if STACK_IGLP >= 0
+    __builtin_amdgcn_iglp_opt(STACK_IGLP);
+#endif
+    const int off = (st >> 1) * 16 + (st & 1) * 4;
+    float a[NS][4];   // plain fma chains, slot order as before
+#pragma unroll
+    for (int q = 0; q < DL; ++q) {
+      const float4 v4 = *reinterpret_cast<const float4*>(xr[q] + off);
+      const float v[4] = {v4.x, v4.y, v4.z, v4.w};
+#pragma unroll
+      for (int h = 0; h < NS; ++h)
+#pragma unroll
+        for (int c = 0; c < 4; ++c) a[h][c] = q == 0 ? wq[h][0] * v[c] : fmaf(wq[h][q], v[c], a[h][c]);
+    }
+#pragma unroll
+    for (int h = 0; h < NS; ++h) stack_mfma4(a[h], bc[h], acc);
+    if (!GAT) {
+      const float4 o = *reinterpret_cast<const float4*>(xo + off);   // root term
+      const float ao[4] = {o.x, o.y, o.z, o.w};
+      stack_mfma4(ao, bc[1], acc);
+    }
+  };
+#else
+  typedef float f2 __attribute__((ext_vector_type(2)));
   // per-lane 32-bit offsets of the B rows (t*32 + li) at this lane half's k; segment h adds h*GF*GF
   const uint32_t boff = (uint32_t)(li * GF + lh * 8);
   auto load_b = [&](int st, float4 (&bw)[GHEADS][2]) {
@@ -430,6 +555,7 @@ __device__ __forceinline__ void stack_layer_k(const float* xs, const float (*al)
       stack_mfma4(ao, bc[1], acc);
     }
   };
+#endif
 #if STACK_PINGPONG
   // ping-pong B buffers: each step's fragments are loaded one step ahead, no register copies
   float4 ba[GHEADS][2], bb[GHEADS][2];
@@ -481,7 +607,7 @@ __device__ __forceinline__ void stack_layer_kh(const float* xs, const float (*al
   constexpr int NS = GAT ? GHEADS : 1;
   constexpr int NSEG = GAT ? GHEADS : 2;
   float wq[NS][DL];
-  stack_edge_weights<DL, GAT>(al, id, node, d0, wq);
+  stack_edge_weights<DL, GAT>(al, id, node, d0, lh, wq);
 #pragma unroll 1
   for (int kc = 0; kc < GF / 16; ++kc) {
     const int off = 16 * kc + 8 * lh;   // this lane's 8 consecutive k of the chunk
@@ -581,7 +707,7 @@ __device__ __forceinline__ void stack_layer_dispatch(int dl, const float* xs, co
 template <bool BF16, int WG = (BF16 ? STACK_WG_PER_CU_BF16 : STACK_WG_PER_CU)>
 __global__ __launch_bounds__(256, WG) void graph_stack_kernel(
     const float* __restrict__ x, int F, int J, const int* __restrict__ nbr_ptr,
-    const int* __restrict__ nbr_idx, GraphStack S, float* __restrict__ y) {
+    const int* __restrict__ nbr_idx, const uint32_t* __restrict__ plan, GraphStack S, float* __restrict__ y) {
   __shared__ __attribute__((aligned(16))) float xs[GMAXN * ZP];        // node-indexed tile
   __shared__ __attribute__((aligned(16))) float Uk[GF][2 * GHEADS];
   __shared__ float al[2 * GHEADS][GMAXN];                              // node-indexed logits
@@ -602,7 +728,6 @@ __global__ __launch_bounds__(256, WG) void graph_stack_kernel(
   const int lane = tid & 63, wave = tid >> 6;
   const int li = lane & 31, lh = lane >> 5;
 
-  const int ne = min(nbr_ptr[J], 2 * GMAXN - (J + 1));
   {
     constexpr int NL = GMAXN * (GF / 4) / 256;
     float4 v[NL];
@@ -618,44 +743,69 @@ __global__ __launch_bounds__(256, WG) void graph_stack_kernel(
       *reinterpret_cast<float4*>(xs + n * ZP + q * 4) = v[j];
     }
   }
-  for (int i = tid; i < J + 1 + ne; i += blockDim.x) csr[i] = i <= J ? nbr_ptr[i] : nbr_idx[i - (J + 1)];
-  __syncthreads();
-  // block-local in-neighbour lists (edge order; the GAT self loop is added per layer)
-  for (int n = tid; n < GMAXN; n += blockDim.x) {
-    int d = 0;
-    if (n < NB) {
-      const int f0 = (n / J) * J, ln = n % J;
-      for (int e = csr[ln]; e < csr[ln + 1] && d < GMAXDEG - 1; ++e) nbl[n][d++] = f0 + csr[J + 1 + e];
-    }
-    for (int q = d; q < GMAXDEG; ++q) nbl[n][q] = 0;
-    ndeg[n] = d;
-    rown[n] = 0xff;
-  }
-  __syncthreads();
-  // rows sorted by degree (descending; stable), the heaviest 32 in wave blockIdx & 3
-  for (int n = tid; n < NB; n += blockDim.x) {
-    const int d = ndeg[n];
-    int pos = 0;
-    for (int m = 0; m < NB; ++m) {
-      const int dm = ndeg[m];
-      pos += (dm > d) || (dm == d && m < n);
-    }
-    rown[((((pos >> 5) + blockIdx.x) & 3) << 5) | (pos & 31)] = (unsigned char)n;
-  }
-  __syncthreads();
-  const int rn = rown[wave * 32 + li];
-  const bool live = rn != 0xff;
-  const int node = live ? rn : 0;
-  const int d0 = live ? ndeg[node] : 0;
-  int ids[GMAXDEG];
-  {
-    const uint2 nb = *reinterpret_cast<const uint2*>(&nbl[node][0]);
-#pragma unroll
-    for (int q = 0; q < GMAXDEG; ++q) ids[q] = live ? ((q < 4 ? nb.x : nb.y) >> (8 * (q & 3))) & 0xff : 0;
-  }
+  bool live;
+  int node, d0;
   int idg[GMAXDEG];   // in-neighbours, then the GAT self loop at slot d0 (weight 0 in GraphConv)
+  if (plan) {
+    // The skeleton's tables come ready from a2m_graph_stack_plan_build: sorted row p of a full
+    // tile sits in wave ((p >> 5) + blockIdx) & 3, so this thread's row is one 12-byte read (both
+    // lane halves the same row; the plan stays in L2).  Rows past the tile's live nodes -- the
+    // plan's padding rows carry node 0xff -- are dead, as in the in-kernel build.
+    const uint32_t* pr = plan + ((((wave - (int)blockIdx.x) & 3) << 5) | li) * (STACK_PLAN_ROW / 4);
+    uint32_t pw[3] = {pr[0], pr[1], pr[2]};
+    live = (int)(pw[0] & 0xff) < NB;
 #pragma unroll
-  for (int q = 0; q < GMAXDEG; ++q) idg[q] = q < d0 ? ids[q] : (q == d0 ? node : 0);
+    for (int j = 0; j < 3; ++j) pw[j] = live ? pw[j] : 0u;
+    node = pw[0] & 0xff;
+    d0 = (pw[0] >> 8) & 0xff;
+#pragma unroll
+    for (int q = 0; q < GMAXDEG; ++q) idg[q] = (pw[(q + 2) >> 2] >> (8 * ((q + 2) & 3))) & 0xff;
+#if !STACK_TEPI
+    if (lh == 0) rown[wave * 32 + li] = live ? (unsigned char)node : 0xff;
+#endif
+    // the tile must be complete before a first-layer GraphConv gathers from it (a GAT layer's
+    // logit barriers order it)
+    if (S.kind[0] != 0 || !STACK_TEPI) __syncthreads();
+  } else {
+    const int ne = min(nbr_ptr[J], 2 * GMAXN - (J + 1));
+    for (int i = tid; i < J + 1 + ne; i += blockDim.x) csr[i] = i <= J ? nbr_ptr[i] : nbr_idx[i - (J + 1)];
+    __syncthreads();
+    // block-local in-neighbour lists (edge order; the GAT self loop is added per layer)
+    for (int n = tid; n < GMAXN; n += blockDim.x) {
+      int d = 0;
+      if (n < NB) {
+        const int f0 = (n / J) * J, ln = n % J;
+        for (int e = csr[ln]; e < csr[ln + 1] && d < GMAXDEG - 1; ++e) nbl[n][d++] = f0 + csr[J + 1 + e];
+      }
+      for (int q = d; q < GMAXDEG; ++q) nbl[n][q] = 0;
+      ndeg[n] = d;
+      rown[n] = 0xff;
+    }
+    __syncthreads();
+    // rows sorted by degree (descending; stable), the heaviest 32 in wave blockIdx & 3
+    for (int n = tid; n < NB; n += blockDim.x) {
+      const int d = ndeg[n];
+      int pos = 0;
+      for (int m = 0; m < NB; ++m) {
+        const int dm = ndeg[m];
+        pos += (dm > d) || (dm == d && m < n);
+      }
+      rown[((((pos >> 5) + blockIdx.x) & 3) << 5) | (pos & 31)] = (unsigned char)n;
+    }
+    __syncthreads();
+    const int rn = rown[wave * 32 + li];
+    live = rn != 0xff;
+    node = live ? rn : 0;
+    d0 = live ? ndeg[node] : 0;
+    int ids[GMAXDEG];
+    {
+      const uint2 nb = *reinterpret_cast<const uint2*>(&nbl[node][0]);
+#pragma unroll
+      for (int q = 0; q < GMAXDEG; ++q) ids[q] = live ? ((q < 4 ? nb.x : nb.y) >> (8 * (q & 3))) & 0xff : 0;
+    }
+#pragma unroll
+    for (int q = 0; q < GMAXDEG; ++q) idg[q] = q < d0 ? ids[q] : (q == d0 ? node : 0);
+  }
   // wave-uniform gather bound: the largest in-degree among this wave's rows
   int dw = d0;
 #pragma unroll
@@ -881,13 +1031,62 @@ extern "C" int a2m_to_bf16_f32(const float* x, void* y, int64_t n, void* stream)
   return A2M_OK;
 }
 
-extern "C" int a2m_graph_stack_fwd_ex_f32(const float* x, int32_t F, int32_t J, const int32_t* nbr_ptr,
-                                          const int32_t* nbr_idx, int32_t nlayers, const int32_t* kinds,
-                                          const float* const* w0, const float* const* w1,
-                                          const float* const* U, const float* const* bias,
-                                          const float* const* ln_w, const float* const* ln_b,
-                                          const void* const* w0h, const void* const* w1h, float slope,
-                                          float* y, void* stream);
+// The stack's topology plan (see GraphStack above), built on the host from the in-neighbour CSR of
+// one J-node graph, with the limits the kernels have: J <= 128, in-degree <= 7, (J + 1) + edges
+// <= 256.  Pure host code: no device call.
+static int stack_plan(int32_t J, const int32_t* nbr_ptr, const int32_t* nbr_idx, void* host, size_t bytes,
+                      size_t* need) {
+  A2M_CHECK_ARG(nbr_ptr && nbr_idx, "graph_stack: null pointer");
+  A2M_CHECK_ARG(J > 0 && J <= GMAXN, "graph_stack: bad J=%d", J);
+  A2M_CHECK_ARG(nbr_ptr[0] == 0, "graph_stack: nbr_ptr[0] = %d, not 0", nbr_ptr[0]);
+  for (int n = 0; n < J; ++n) {
+    const int d = nbr_ptr[n + 1] - nbr_ptr[n];
+    A2M_CHECK_ARG(d >= 0, "graph_stack: nbr_ptr decreases at node %d", n);
+    A2M_CHECK_ARG(d <= GMAXDEG - 1,
+                  "graph_stack: node %d has in-degree %d: the graph kernels support at most %d (+ the GAT self loop)",
+                  n, d, GMAXDEG - 1);
+  }
+  const int ne = nbr_ptr[J];
+  A2M_CHECK_ARG(J + 1 + ne <= 2 * GMAXN,
+                "graph_stack: %d edges over %d nodes: the graph kernels hold at most %d edges for this node count",
+                ne, J, 2 * GMAXN - (J + 1));
+  for (int e = 0; e < ne; ++e)
+    A2M_CHECK_ARG(nbr_idx[e] >= 0 && nbr_idx[e] < J, "graph_stack: edge %d from node %d outside [0, %d)", e,
+                  nbr_idx[e], J);
+  *need = STACK_PLAN_BYTES;
+  if (!host) return A2M_OK;
+  A2M_CHECK_ARG(bytes >= STACK_PLAN_BYTES, "graph_stack: plan buffer of %zu bytes, %zu needed", bytes,
+                STACK_PLAN_BYTES);
+  unsigned char* p = static_cast<unsigned char*>(host);
+  std::memset(p, 0, STACK_PLAN_BYTES);
+  const int nb = (GMAXN / J) * J;
+  int row = 0;
+  // degree descending, node index ascending within a degree: the kernel's stable rank order
+  for (int d = GMAXDEG - 1; d >= 0; --d)
+    for (int n = 0; n < nb; ++n) {
+      const int ln = n % J, f0 = n - ln;
+      if (nbr_ptr[ln + 1] - nbr_ptr[ln] != d) continue;
+      unsigned char* r = p + (size_t)row++ * STACK_PLAN_ROW;
+      r[0] = (unsigned char)n;
+      r[1] = (unsigned char)d;
+      for (int q = 0; q < d; ++q) r[2 + q] = (unsigned char)(f0 + nbr_idx[nbr_ptr[ln] + q]);
+      r[2 + d] = (unsigned char)n;
+    }
+  for (; row < GMAXN; ++row) p[(size_t)row * STACK_PLAN_ROW] = 0xff;
+  return A2M_OK;
+}
+
+extern "C" size_t a2m_graph_stack_plan_bytes(int32_t J, const int32_t* nbr_ptr, const int32_t* nbr_idx) {
+  size_t need = 0;
+  if (stack_plan(J, nbr_ptr, nbr_idx, nullptr, 0, &need)) return 0;
+  return need;
+}
+
+extern "C" int a2m_graph_stack_plan_build(int32_t J, const int32_t* nbr_ptr, const int32_t* nbr_idx,
+                                          void* host_plan, size_t plan_bytes) {
+  size_t need = 0;
+  return stack_plan(J, nbr_ptr, nbr_idx, host_plan, plan_bytes, &need);
+}
 
 extern "C" int a2m_graph_stack_fwd_f32(const float* x, int32_t F, int32_t J, const int32_t* nbr_ptr,
                                        const int32_t* nbr_idx, int32_t nlayers, const int32_t* kinds,
@@ -895,8 +1094,8 @@ extern "C" int a2m_graph_stack_fwd_f32(const float* x, int32_t F, int32_t J, con
                                        const float* const* U, const float* const* bias,
                                        const float* const* ln_w, const float* const* ln_b,
                                        float slope, float* y, void* stream) {
-  return a2m_graph_stack_fwd_ex_f32(x, F, J, nbr_ptr, nbr_idx, nlayers, kinds, w0, w1, U, bias, ln_w, ln_b,
-                                    nullptr, nullptr, slope, y, stream);
+  return a2m_graph_stack_fwd_ex2_f32(x, F, J, nbr_ptr, nbr_idx, nlayers, kinds, w0, w1, U, bias, ln_w, ln_b,
+                                     nullptr, nullptr, nullptr, slope, y, stream);
 }
 
 extern "C" int a2m_graph_stack_fwd_ex_f32(const float* x, int32_t F, int32_t J, const int32_t* nbr_ptr,
@@ -906,7 +1105,19 @@ extern "C" int a2m_graph_stack_fwd_ex_f32(const float* x, int32_t F, int32_t J, 
                                           const float* const* ln_w, const float* const* ln_b,
                                           const void* const* w0h, const void* const* w1h, float slope,
                                           float* y, void* stream) {
+  return a2m_graph_stack_fwd_ex2_f32(x, F, J, nbr_ptr, nbr_idx, nlayers, kinds, w0, w1, U, bias, ln_w, ln_b,
+                                     w0h, w1h, nullptr, slope, y, stream);
+}
+
+extern "C" int a2m_graph_stack_fwd_ex2_f32(const float* x, int32_t F, int32_t J, const int32_t* nbr_ptr,
+                                           const int32_t* nbr_idx, int32_t nlayers, const int32_t* kinds,
+                                           const float* const* w0, const float* const* w1,
+                                           const float* const* U, const float* const* bias,
+                                           const float* const* ln_w, const float* const* ln_b,
+                                           const void* const* w0h, const void* const* w1h,
+                                           const void* plan, float slope, float* y, void* stream) {
   A2M_CHECK_ARG(w0 && w1, "graph_stack: null pointer");
+  A2M_CHECK_ARG((reinterpret_cast<uintptr_t>(plan) & 3) == 0, "graph_stack: plan not 4-byte aligned");
   A2M_CHECK_ARG(x && y && nbr_ptr && nbr_idx && kinds && U && bias && ln_w && ln_b,
                 "graph_stack: null pointer");
   A2M_CHECK_ARG(J > 0 && J <= GMAXN && F >= 0, "graph_stack: bad J=%d", J);
@@ -936,18 +1147,19 @@ extern "C" int a2m_graph_stack_fwd_ex_f32(const float* x, int32_t F, int32_t J, 
   }
   if (F == 0) return A2M_OK;
   const int fpb = GMAXN / J;
+  const uint32_t* pl = static_cast<const uint32_t*>(plan);
   if (S.bf16 && J > 32 && STACK_WG_PER_CU_BF16_WIDE != STACK_WG_PER_CU_BF16)
     hipLaunchKernelGGL((graph_stack_kernel<true, STACK_WG_PER_CU_BF16_WIDE>), dim3((unsigned)cdiv(F, fpb)), dim3(256),
-                       0, as_stream(stream), x, F, J, nbr_ptr, nbr_idx, S, y);
+                       0, as_stream(stream), x, F, J, nbr_ptr, nbr_idx, pl, S, y);
   else if (S.bf16)
     hipLaunchKernelGGL(graph_stack_kernel<true>, dim3((unsigned)cdiv(F, fpb)), dim3(256), 0, as_stream(stream),
-                       x, F, J, nbr_ptr, nbr_idx, S, y);
+                       x, F, J, nbr_ptr, nbr_idx, pl, S, y);
   else if (J > 32 && STACK_WG_PER_CU_WIDE != STACK_WG_PER_CU)
     hipLaunchKernelGGL((graph_stack_kernel<false, STACK_WG_PER_CU_WIDE>), dim3((unsigned)cdiv(F, fpb)), dim3(256),
-                       0, as_stream(stream), x, F, J, nbr_ptr, nbr_idx, S, y);
+                       0, as_stream(stream), x, F, J, nbr_ptr, nbr_idx, pl, S, y);
   else
     hipLaunchKernelGGL(graph_stack_kernel<false>, dim3((unsigned)cdiv(F, fpb)), dim3(256), 0, as_stream(stream),
-                       x, F, J, nbr_ptr, nbr_idx, S, y);
+                       x, F, J, nbr_ptr, nbr_idx, pl, S, y);
   A2M_LAUNCH_CHECK();
   return A2M_OK;
 }

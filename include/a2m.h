@@ -361,6 +361,28 @@ int a2m_graph_stack_fwd_ex_f32(const float* x, int32_t F, int32_t J, const int32
                                const float* const* bias, const float* const* ln_w,
                                const float* const* ln_b, const void* const* w0h,
                                const void* const* w1h, float slope, float* y, void* stream);
+/* The stack's topology plan: the degree-sorted row order, the in-degrees and the gather slots of
+ * one full workgroup tile (128 / J frames), which depend on the skeleton alone.  Built on the HOST
+ * from the in-neighbour CSR as host arrays -- no device call -- and copied to device memory once by
+ * the caller, like the a2m_logmel_* plan.  a2m_graph_stack_plan_build checks the topology limits
+ * above and returns A2M_EINVAL beyond them; a2m_graph_stack_plan_bytes returns 0 then.
+ * Layout: 128 rows of 12 bytes in sorted-row order (in-degree descending, node index ascending
+ * within a degree): node, in-degree d, 8 gather slots (the in-neighbours in edge order as
+ * tile-local node indices f * J + source, the node itself at slot d, 0 after), 2 bytes of
+ * padding; rows past the tile's (128 / J) * J nodes carry node 0xff. */
+size_t a2m_graph_stack_plan_bytes(int32_t J, const int32_t* nbr_ptr, const int32_t* nbr_idx);
+int a2m_graph_stack_plan_build(int32_t J, const int32_t* nbr_ptr, const int32_t* nbr_idx,
+                               void* host_plan, size_t plan_bytes);
+/* a2m_graph_stack_fwd_ex_f32 with the plan (device memory, 4-byte aligned, built for this J and
+ * CSR): the workgroups read their rows from it instead of rebuilding the tables in LDS.  The
+ * result is that of plan = NULL, which is a2m_graph_stack_fwd_ex_f32. */
+int a2m_graph_stack_fwd_ex2_f32(const float* x, int32_t F, int32_t J, const int32_t* nbr_ptr,
+                                const int32_t* nbr_idx, int32_t nlayers, const int32_t* kinds,
+                                const float* const* w0, const float* const* w1, const float* const* U,
+                                const float* const* bias, const float* const* ln_w,
+                                const float* const* ln_b, const void* const* w0h,
+                                const void* const* w1h, const void* plan, float slope, float* y,
+                                void* stream);
 /* y[i] = bf16(x[i]), round to nearest even (the rounding the bf16 operand mode applies), n
  * elements; y 4-byte aligned, 2 bytes an element. */
 int a2m_to_bf16_f32(const float* x, void* y, int64_t n, void* stream);
