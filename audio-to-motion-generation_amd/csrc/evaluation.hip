@@ -60,7 +60,12 @@ __global__ void pose_denormalize_kernel(const float* __restrict__ pose, int64_t 
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n * PF;
        i += (int64_t)gridDim.x * blockDim.x) {
     const int j = (int)(i % PF);
-    out[i] = __fadd_rn(__fmul_rn(pose[i], std_[j]), mean[j]);
+    // two roundings, as torch's x * std + mean.  The build (-ffp-contract=fast) fuses a product and
+    // a sum into one multiply-add in the back end, through __fmul_rn / __fadd_rn and through
+    // "#pragma clang fp contract(off)" alike; a value that passes an empty asm cannot be fused.
+    float scaled = pose[i] * std_[j];
+    asm volatile("" : "+v"(scaled));
+    out[i] = scaled + mean[j];
   }
 }
 
@@ -110,7 +115,9 @@ int a2m_pose_moments_f32(const float* pose, int64_t n_frames, int32_t necksub, d
 
 int a2m_pose_normalize_f32(const float* pose, int64_t n_frames, const float* mean, const float* std_,
                            float* out, void* stream) {
-  A2M_CHECK_ARG(pose && mean && std_ && out && n_frames >= 0, "pose_normalize: bad args");
+  // an empty batch is a no-op and may come with null pointers (an empty tensor has none)
+  A2M_CHECK_ARG(n_frames >= 0 && (n_frames == 0 || (pose && mean && std_ && out)),
+                "pose_normalize: bad args");
   if (n_frames == 0) return A2M_OK;
   const int blocks = (int)std::min<int64_t>(cdiv(n_frames * PF, 256), 4096);
   hipLaunchKernelGGL(pose_normalize_kernel, dim3(blocks), dim3(256), 0, as_stream(stream), pose,
@@ -121,7 +128,8 @@ int a2m_pose_normalize_f32(const float* pose, int64_t n_frames, const float* mea
 
 int a2m_pose_denormalize_f32(const float* pose, int64_t n_frames, const float* mean,
                              const float* std_, float* out, void* stream) {
-  A2M_CHECK_ARG(pose && mean && std_ && out && n_frames >= 0, "pose_denormalize: bad args");
+  A2M_CHECK_ARG(n_frames >= 0 && (n_frames == 0 || (pose && mean && std_ && out)),
+                "pose_denormalize: bad args");
   if (n_frames == 0) return A2M_OK;
   const int blocks = (int)std::min<int64_t>(cdiv(n_frames * PF, 256), 4096);
   hipLaunchKernelGGL(pose_denormalize_kernel, dim3(blocks), dim3(256), 0, as_stream(stream), pose,
@@ -132,7 +140,7 @@ int a2m_pose_denormalize_f32(const float* pose, int64_t n_frames, const float* m
 
 int a2m_pck_f32(const float* pred, const float* gt, int32_t N, int32_t K, double alpha,
                 double* out, void* stream) {
-  A2M_CHECK_ARG(pred && gt && out && N >= 0 && K > 0, "pck: bad args");
+  A2M_CHECK_ARG(N >= 0 && K > 0 && (N == 0 || (pred && gt && out)), "pck: bad args");
   if (N == 0) return A2M_OK;
   hipLaunchKernelGGL(pck_kernel, dim3((unsigned)cdiv(N, 4)), dim3(256), 0, as_stream(stream), pred, gt,
                      N, K, alpha, out);
@@ -170,8 +178,8 @@ extern "C" int a2m_window_gather_f32(const float* data, int64_t length, int32_t 
                                      const int64_t* starts, int32_t n_windows, int32_t window,
                                      int32_t interval, const float* mean, const float* std_,
                                      float* out, void* stream) {
-  A2M_CHECK_ARG(data && starts && out && C > 0 && n_windows >= 0 && window > 0 && interval > 0 &&
-                    (mean == nullptr) == (std_ == nullptr),
+  A2M_CHECK_ARG(C > 0 && n_windows >= 0 && window > 0 && interval > 0 &&
+                    (mean == nullptr) == (std_ == nullptr) && (n_windows == 0 || (data && starts && out)),
                 "window_gather: bad args");
   (void)length;  // the host computed starts < length - window (dataUtils.py:611-618)
   if (n_windows == 0) return A2M_OK;

@@ -215,7 +215,7 @@ __global__ __launch_bounds__(256) void motion_terms_kernel(const float* fake, co
     part[3 * b + 1] = (float)sa;
     part[3 * b + 2] = (float)sj;
   }
-  if (!dfake || !gterms) return;
+  if (!dfake || !gterms) return;  // the entry point takes the two together or not at all
   // gradient w.r.t. motion m[t][f] (t < T-1), then the diff adjoint
   const float w1 = gterms[0], ws_ = gterms[1], wj = gterms[2];
   const float cl1 = rp ? w1 / (float)(B * (T - 1) * Fd) : 0.f;
@@ -440,7 +440,9 @@ int a2m_pose_losses_bwd_f32(const float* gen, int64_t gs_b, int64_t gs_t, const 
 int a2m_motion_losses_f32(const float* fake, const float* real, int32_t B, int32_t T, int32_t Fd,
                           float* terms, const float* grad_terms, float* dfake, void* ws,
                           size_t ws_bytes, void* stream) {
-  A2M_CHECK_ARG(fake && terms && B > 0 && T > 1 && T <= 512 && Fd > 0, "motion_losses: bad args");
+  A2M_CHECK_ARG(fake && terms && B > 0 && T > 1 && T <= 512 && Fd > 0 &&
+                    (grad_terms == nullptr) == (dfake == nullptr),
+                "motion_losses: bad args");
   const size_t need = sizeof(float) * 3 * (size_t)B;
   if (!ws || ws_bytes < need) { set_error("motion_losses: workspace too small (%zu < %zu bytes)", ws_bytes, need); return A2M_EWS; }
   hipStream_t st = as_stream(stream);
@@ -533,8 +535,9 @@ int a2m_gather_segments_f32(const float* const* src, const int64_t* dst_off, con
     const int m = std::min(GS_MAX, count - c0);
     int64_t maxn = 0;
     for (int i = 0; i < m; ++i) {
-      A2M_CHECK_ARG(src[c0 + i] && n[c0 + i] >= 0 && dst_off[c0 + i] >= 0, "gather_segments: segment %d",
-                    c0 + i);
+      // an empty segment needs no source (an empty tensor has a null pointer)
+      A2M_CHECK_ARG(n[c0 + i] >= 0 && dst_off[c0 + i] >= 0 && (src[c0 + i] || n[c0 + i] == 0),
+                    "gather_segments: segment %d", c0 + i);
       segs.src[i] = src[c0 + i];
       segs.off[i] = dst_off[c0 + i];
       segs.n[i] = n[c0 + i];

@@ -565,7 +565,10 @@ int a2m_graph_layer_bwd_saved_f32(const float* x, const float* dy, const float* 
 int a2m_interp_time_bwd_f32(const float* dy, int32_t B, int32_t C, int32_t H, int32_t W,
                             float* dx, int32_t T, void* stream);
 
-/* Losses of the G / D steps (version5_model_train.py:208-248, 367-403). */
+/* Losses of the G / D steps (version5_model_train.py:208-248, 367-403).
+ * The pose-loss backward ADDS grad_out[0] d bone / d gen + grad_out[1] d angle / d gen into dgen
+ * ([B][T][104] contiguous): the caller zeroes dgen first, or passes a gradient to add to.  With
+ * real == NULL there is no bone term (grad_out[0] is not used). */
 int a2m_pose_losses_bwd_f32(const float* gen, int64_t gs_b, int64_t gs_t, const float* real,
                             int64_t rs_b, int64_t rs_t, int32_t B, int32_t T,
                             const float* grad_out, float* dgen, void* ws, size_t ws_bytes,
@@ -575,8 +578,12 @@ int a2m_pose_losses_w_bwd_f32(const float* gen, int64_t gs_b, int64_t gs_t, cons
                               float body_w, const float* grad_out, float* dgen, void* ws,
                               size_t ws_bytes, void* stream);
 /* terms = [L1(diff(real), diff(fake)), mean||accel||, mean||jerk||] on [B][T][Fd] (contiguous).
- * If grad_terms (device [3], the incoming dL/dterms) and dfake are given, also
- * dfake = sum_i grad_terms[i] * dterms[i]/dfake (overwritten). */
+ * 2 <= T <= 512.  A term over no frames is 0, not the NaN of an empty mean: terms[1] = 0 at
+ * T = 2 and terms[2] = 0 at T <= 3, and such a term adds nothing to dfake; terms[0] = 0 and has
+ * no gradient if real == NULL.
+ * grad_terms (device [3], the incoming dL/dterms) and dfake come together: with both,
+ * dfake = sum_i grad_terms[i] * dterms[i]/dfake (overwritten; 0 through a zero norm or a zero
+ * L1 difference, as torch); with neither, only the terms; one without the other is A2M_EINVAL. */
 int a2m_motion_losses_f32(const float* fake, const float* real, int32_t B, int32_t T, int32_t Fd,
                           float* terms, const float* grad_terms, float* dfake, void* ws,
                           size_t ws_bytes, void* stream);
@@ -637,7 +644,8 @@ int a2m_adam_dev_f32(float* param, const float* grad, float* exp_avg, float* exp
                      int32_t* step, void* stream);
 
 /* dst[dst_off[i] .. dst_off[i] + n[i]) = src[i][0 .. n[i]) for i < count (host arrays of device
- * pointers / element counts; segments must not overlap).  The optimiser's gradient collection:
+ * pointers / element counts; segments must not overlap; src[i] may be NULL where n[i] = 0).
+ * The optimiser's gradient collection:
  * per-parameter gradient tensors into the flat gradient buffer, 48 segments per launch.
  * Replaces torch's per-parameter AccumulateGrad add (version5_model_train.py:285-286 Adam over
  * model.parameters()). */
@@ -652,7 +660,9 @@ int a2m_gather_segments_f32(const float* const* src, const int64_t* dst_off, con
  * a2m_pose_normalize_f32: ((x - neck) - mean) / std  (version5_model_train.py:298-304).
  * a2m_pose_denormalize_f32: x * std + mean  (generate_motion_video.py:259-260).
  * a2m_pck_f32: pred, gt [N][2][K] -> out[N] = fraction of keypoints with
- * |gt - pred| <= alpha * max(x extent, y extent) of gt (motion_evaluation.py:4-22). */
+ * |gt - pred| <= alpha * max(x extent, y extent) of gt (motion_evaluation.py:4-22).
+ * normalize / denormalize with n_frames = 0 and pck with N = 0 do nothing and accept NULL data
+ * pointers (an empty batch has none). */
 int a2m_pose_moments_f32(const float* pose, int64_t n_frames, int32_t necksub, double* acc,
                          void* stream);
 int a2m_pose_normalize_f32(const float* pose, int64_t n_frames, const float* mean, const float* std_,
@@ -664,7 +674,8 @@ int a2m_pck_f32(const float* pred, const float* gt, int32_t N, int32_t K, double
 
 /* PATS windowing (dataUtils.py:585-665): out[w][j][c] =
  * data[starts[w] + j*interval][c], j < ceil(window/interval), data [length][C] in HBM; with
- * mean/std (both or neither) each value is standardised as (x - mean[c]) / (std[c] < 1e-7 ? 1 : std[c]). */
+ * mean/std (both or neither) each value is standardised as (x - mean[c]) / (std[c] < 1e-7 ? 1 : std[c]).
+ * n_windows = 0 does nothing and accepts NULL data, starts and out. */
 int a2m_window_gather_f32(const float* data, int64_t length, int32_t C, const int64_t* starts,
                           int32_t n_windows, int32_t window, int32_t interval, const float* mean,
                           const float* std_, float* out, void* stream);
