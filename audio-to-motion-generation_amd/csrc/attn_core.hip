@@ -486,7 +486,8 @@ __global__ __launch_bounds__(NV == 64 ? 512 : 768, NV == 64 ? 2 : 1) void attn_f
   }
 }
 
-bool attn_fused_eval_fits(int C, int T) { return T <= AT && T % 4 == 0 && (C == 128 || C == 256); }
+// T >= 4: T = 0 and T = -4 are multiples of 4 too, and the eval entries rest on this check alone
+bool attn_fused_eval_fits(int C, int T) { return T >= 4 && T <= AT && T % 4 == 0 && (C == 128 || C == 256); }
 
 // ---------------------------------------------------------------------------------------
 // Wide queries, short sequences: the UNet's SelfAttention(2048) at T = 16 / 32 (bottleneck and

@@ -252,9 +252,11 @@ __global__ __launch_bounds__(256) void channel_att_fused256_kernel(const float* 
   }
 }
 
-// y[b][c][t] = x[b][c][t] * att[b][c], float4 along T when T % 4 == 0.
-__global__ void channel_scale_kernel(const float* x, const float* att, int T, int64_t n, float* y) {
-  if ((T & 3) == 0) {
+// y[b][c][t] = x[b][c][t] * att[b][c], float4 along T when vec (the host sets it at T % 4 == 0
+// with x and y 16-byte aligned).
+__global__ void channel_scale_kernel(const float* x, const float* att, int T, int64_t n, float* y,
+                                     int vec) {
+  if (vec) {
     const int64_t n4 = n >> 2;
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n4;
          i += (int64_t)gridDim.x * blockDim.x) {
@@ -1382,6 +1384,14 @@ int a2m_stack_qkv_f32(const float* wq, const float* bq, const float* wk, const f
   return stack_qkv(wq, bq, wk, bk, wv, bv, C, wqkv, bqkv, as_stream(stream));
 }
 
+int32_t a2m_self_attention_route(int32_t C, int32_t T, int32_t keep) {
+  if (C < 8 || C % 8 != 0 || T <= 0) return 0;
+  if (!keep && attn_fused_eval_fits(C, T)) return 3;
+  if (attn_core_fits(C, T)) return 1;
+  if (attn_core_wide_fits(C, T)) return 2;
+  return 0;
+}
+
 int a2m_self_attention_packed_fwd_f32(const float* x, int64_t x_bs, int32_t B, int32_t C,
                                       int32_t T, const float* wqkv, const float* bqkv,
                                       const float* gamma, const float* res, float* y, int64_t y_bs,
@@ -1430,9 +1440,10 @@ int a2m_self_attention_packed_fwd_f32(const float* x, int64_t x_bs, int32_t B, i
                             ws_bytes, stream);
   }
   if (rc) return rc;
-  if (attn_core_fits(C, T))
+  const int route = a2m_self_attention_route(C, T, 1);
+  if (route == 1)
     return attn_core(qkv, qs_b, B, C, T, gamma, x, x_bs, res, y, attn, st);
-  if (attn_core_wide_fits(C, T))   // the UNet's / D's SelfAttention(2048), T <= 32
+  if (route == 2)   // the UNet's / D's SelfAttention(2048), T <= 32
     return attn_core_wide(qkv, qs_b, B, C, T, gamma, x, x_bs, res, y, attn, st);
   // scores[b][i][j] = sum_c q[b][c][i] k[b][c][j]
   Gather Aq = dense_kr(qkv, T, qs_b);
@@ -1546,7 +1557,10 @@ int a2m_channel_attention_fwd_f32(const float* x, int32_t B, int32_t C, int32_t 
   A2M_LAUNCH_CHECK();
   const int64_t n = (int64_t)B * C * T;
   const int blocks = (int)std::min<int64_t>(cdiv(n / 4 + 1, 256), 2048);
-  hipLaunchKernelGGL(channel_scale_kernel, dim3(blocks), dim3(256), 0, st, x, att_out, T, n, y);
+  // float4 runs only from 16-byte aligned x and y: a contiguous view may start at any float
+  const int vec = (T & 3) == 0 &&
+                  ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y)) & 15) == 0;
+  hipLaunchKernelGGL(channel_scale_kernel, dim3(blocks), dim3(256), 0, st, x, att_out, T, n, y, vec);
   A2M_LAUNCH_CHECK();
   return A2M_OK;
 }

@@ -48,25 +48,32 @@ __global__ __launch_bounds__(256) void sum_vector_kernel(const float* x, int n, 
 // partials per batch element go to part[b][W1 (Cr*C) | b1 (Cr) | W2 (C*Cr) | b2 (C)].
 // The reductions over channels / time run on groups of 8 lanes (strided partial sums, then
 // three xor shuffles), so every phase keeps all waves busy instead of one thread per output.
+// The per-clip chain between the pools and the gradients -- pooled means, the MLP, its sigmoids,
+// dz and dh, O(C Cr) operations beside the O(C T) pass over x -- runs in float64: dh = W2^T dz is a
+// sum of signed terms (dz carries dy's sign) that cancels, 24-fold at C = 8 in
+// tests/test_gpu_attention_fp64.py, and every float32 rounding upstream of it reaches db1, dW1
+// and dx multiplied by that factor.  Results are rounded to float32 once, where they are stored.
 constexpr int CAB_NT = 512, CAB_G = 8;
-__device__ __forceinline__ float group8_sum(float v) {
+__device__ __forceinline__ double group8_sum(double v) {
   v += __shfl_xor(v, 1);
   v += __shfl_xor(v, 2);
   return v + __shfl_xor(v, 4);
 }
+// LDS floats of the kernel: pavg, da / dpool (2C each), dz (4C), pmax, att, amax (C each), h, dh (4Cr each)
+static size_t cab_lds_bytes(int C, int Cr) { return sizeof(float) * (11 * (size_t)C + 8 * (size_t)Cr); }
 __global__ __launch_bounds__(CAB_NT) void channel_attention_bwd_kernel(
     const float* dy, const float* x, int C, int T, const float* w1, const float* b1, int Cr,
     const float* w2, const float* b2, float* dx, float* part) {
   extern __shared__ __attribute__((aligned(16))) float sm[];
-  float* pavg = sm;              // C
-  float* pmax = pavg + C;        // C
-  int* amax = reinterpret_cast<int*>(pmax + C);  // C
-  float* h = reinterpret_cast<float*>(amax + C); // 2*Cr
-  float* s = h + 2 * Cr;         // 2*C (sigmoids)
-  float* dz = s + 2 * C;         // 2*C
-  float* dh = dz + 2 * C;        // 2*Cr
-  float* dpool = dh + 2 * Cr;    // 2*C (davg, dmax)
-  float* att = dpool + 2 * C;    // C
+  double* pavg = reinterpret_cast<double*>(sm);  // C
+  double* dz = pavg + C;                         // 2*C
+  double* h = dz + 2 * C;                        // 2*Cr
+  double* dh = h + 2 * Cr;                       // 2*Cr
+  double* dad = dh + 2 * Cr;                     // C: da = sum_t dy*x, until dpool takes its place
+  float* dpool = reinterpret_cast<float*>(dad);  // 2*C (davg, dmax)
+  float* pmax = dpool + 2 * C;                   // C
+  float* att = pmax + C;                         // C
+  int* amax = reinterpret_cast<int*>(att + C);   // C
   const int b = blockIdx.x;
   const float* xb = x + (int64_t)b * C * T;
   const float* gb = dy + (int64_t)b * C * T;
@@ -79,12 +86,13 @@ __global__ __launch_bounds__(CAB_NT) void channel_attention_bwd_kernel(
   for (int c = grp; c < C; c += NGRP) {
     const float* p = xb + (int64_t)c * T;
     const float* q = gb + (int64_t)c * T;
-    float sm_ = 0.f, mx = -INFINITY, da = 0.f;
+    double sm_ = 0.0, da = 0.0;
+    float mx = -INFINITY;
     int ai = T;
     for (int t = gl; t < T; t += CAB_G) {
       const float v = p[t];
       sm_ += v;
-      da += v * q[t];
+      da += (double)v * q[t];
       if (v > mx) { mx = v; ai = t; }
     }
 #pragma unroll
@@ -96,68 +104,71 @@ __global__ __launch_bounds__(CAB_NT) void channel_attention_bwd_kernel(
       if (om > mx || (om == mx && oi < ai)) { mx = om; ai = oi; }
     }
     if (gl == 0) {
-      pavg[c] = sm_ / (float)T;
+      pavg[c] = sm_ / (double)T;
       pmax[c] = mx;
       amax[c] = ai;
-      dpool[c] = da;  // temporarily holds da
+      dad[c] = da;
     }
   }
   __syncthreads();
   // h = relu(W1 pooled + b1) for both pools: one 8-lane group per output
   for (int j = grp; j < 2 * Cr; j += NGRP) {
     const int r = j % Cr;
-    const float* in = j < Cr ? pavg : pmax;
-    float a = 0.f;
-    for (int c = gl; c < C; c += CAB_G) a += w1[(int64_t)r * C + c] * in[c];
-    a = group8_sum(a) + b1[r];
-    if (gl == 0) h[j] = a > 0.f ? a : 0.f;
+    double a = 0.0;
+    if (j < Cr) {
+      for (int c = gl; c < C; c += CAB_G) a += (double)w1[(int64_t)r * C + c] * pavg[c];
+    } else {
+      for (int c = gl; c < C; c += CAB_G) a += (double)w1[(int64_t)r * C + c] * (double)pmax[c];
+    }
+    a = group8_sum(a) + (double)b1[r];
+    if (gl == 0) h[j] = a > 0.0 ? a : 0.0;
   }
   __syncthreads();
   for (int c = tid; c < C; c += CAB_NT) {
-    float a0 = b2[c], a1 = b2[c];
+    double a0 = b2[c], a1 = b2[c];
     for (int r = 0; r < Cr; ++r) {
-      a0 += w2[(int64_t)c * Cr + r] * h[r];
-      a1 += w2[(int64_t)c * Cr + r] * h[Cr + r];
+      const double w = w2[(int64_t)c * Cr + r];
+      a0 += w * h[r];
+      a1 += w * h[Cr + r];
     }
-    const float s0 = 1.f / (1.f + expf(-a0)), s1 = 1.f / (1.f + expf(-a1));
-    s[c] = s0;
-    s[C + c] = s1;
-    att[c] = s0 + s1;
-    const float da = dpool[c];
-    dz[c] = da * s0 * (1.f - s0);
-    dz[C + c] = da * s1 * (1.f - s1);
+    const double s0 = 1.0 / (1.0 + exp(-a0)), s1 = 1.0 / (1.0 + exp(-a1));
+    att[c] = (float)(s0 + s1);
+    const double da = dad[c];
+    dz[c] = da * s0 * (1.0 - s0);
+    dz[C + c] = da * s1 * (1.0 - s1);
   }
   __syncthreads();
   // dW2[c][r] = dz1[c] h1[r] + dz2[c] h2[r]; db2[c] = dz1 + dz2
   for (int i = tid; i < C * Cr; i += CAB_NT) {
     const int c = i / Cr, r = i - c * Cr;
-    pb[Cr * C + Cr + i] = dz[c] * h[r] + dz[C + c] * h[Cr + r];
+    pb[Cr * C + Cr + i] = (float)(dz[c] * h[r] + dz[C + c] * h[Cr + r]);
   }
-  for (int c = tid; c < C; c += CAB_NT) pb[2 * Cr * C + Cr + c] = dz[c] + dz[C + c];
+  for (int c = tid; c < C; c += CAB_NT) pb[2 * Cr * C + Cr + c] = (float)(dz[c] + dz[C + c]);
   // dh = W2^T dz * relu'
   for (int j = grp; j < 2 * Cr; j += NGRP) {
     const int r = j % Cr;
-    const float* d = j < Cr ? dz : dz + C;
-    float a = 0.f;
-    for (int c = gl; c < C; c += CAB_G) a += w2[(int64_t)c * Cr + r] * d[c];
+    const double* d = j < Cr ? dz : dz + C;
+    double a = 0.0;
+    for (int c = gl; c < C; c += CAB_G) a += (double)w2[(int64_t)c * Cr + r] * d[c];
     a = group8_sum(a);
-    if (gl == 0) dh[j] = h[j] > 0.f ? a : 0.f;
+    if (gl == 0) dh[j] = h[j] > 0.0 ? a : 0.0;
   }
-  __syncthreads();
+  __syncthreads();   // every read of da is two barriers back: dpool may overlay it
   // dW1[r][c] = dh1[r] avg[c] + dh2[r] max[c]; db1[r] = dh1 + dh2; dpool = W1^T dh
   for (int i = tid; i < Cr * C; i += CAB_NT) {
     const int r = i / C, c = i - r * C;
-    pb[i] = dh[r] * pavg[c] + dh[Cr + r] * pmax[c];
+    pb[i] = (float)(dh[r] * pavg[c] + dh[Cr + r] * (double)pmax[c]);
   }
-  for (int r = tid; r < Cr; r += CAB_NT) pb[Cr * C + r] = dh[r] + dh[Cr + r];
+  for (int r = tid; r < Cr; r += CAB_NT) pb[Cr * C + r] = (float)(dh[r] + dh[Cr + r]);
   for (int c = tid; c < C; c += CAB_NT) {
-    float a0 = 0.f, a1 = 0.f;
+    double a0 = 0.0, a1 = 0.0;
     for (int r = 0; r < Cr; ++r) {
-      a0 += w1[(int64_t)r * C + c] * dh[r];
-      a1 += w1[(int64_t)r * C + c] * dh[Cr + r];
+      const double w = w1[(int64_t)r * C + c];
+      a0 += w * dh[r];
+      a1 += w * dh[Cr + r];
     }
-    dpool[c] = a0 / (float)T;
-    dpool[C + c] = a1;
+    dpool[c] = (float)(a0 / (double)T);
+    dpool[C + c] = (float)a1;
   }
   __syncthreads();
   float* db_ = dx + (int64_t)b * C * T;
@@ -316,7 +327,7 @@ int a2m_channel_attention_bwd_f32(const float* dy, const float* x, int32_t B, in
     set_error("channel_attention_bwd: workspace too small (%zu < %zu bytes)", ws_bytes, need);
     return A2M_EWS;
   }
-  const size_t lds = sizeof(float) * (10 * (size_t)C + 4 * Cr);
+  const size_t lds = cab_lds_bytes(C, Cr);
   A2M_CHECK_ARG(lds <= 64 * 1024, "channel_attention_bwd: C too large");
   hipStream_t st = as_stream(stream);
   float* part = static_cast<float*>(ws);

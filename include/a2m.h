@@ -288,10 +288,16 @@ int a2m_self_attention_packed_fwd_f32(const float* x, int64_t x_bs, int32_t B, i
                                       const float* gamma, const float* res, float* y, int64_t y_bs,
                                       float* qkv_out, float* attn_out, void* ws, size_t ws_bytes,
                                       void* stream);
+/* Which kernels SelfAttention runs at (C, T), a pure host function: 0 the general path (score
+ * GEMM, softmax, PV GEMM), 1 the attention core (C/8 in {16, 32, 48, 64}, T <= 64), 2 the wide
+ * core (C/8 in {128, 192, 256}, T <= 32, T % 4 == 0), 3 the fused inference kernel, returned only
+ * when keep == 0 (no intermediates wanted) and a2m_self_attention_eval_fits(C, T).
+ * a2m_self_attention_packed_fwd_f32 takes its decision from this function with keep = 1. */
+int32_t a2m_self_attention_route(int32_t C, int32_t T, int32_t keep);
 
 /* Inference-only SelfAttention with the q/k/v projections fused into the attention core (one
  * launch; no qkv / attention intermediates).  Supported when a2m_self_attention_eval_fits(C, T):
- * C in {128, 256}, T <= 64, T % 4 == 0 (the decoders' SelfAttention(256) at T = 64).
+ * C in {128, 256}, 4 <= T <= 64, T % 4 == 0 (the decoders' SelfAttention(256) at T = 64).
  * Same arguments and results as a2m_self_attention_packed_fwd_f32 otherwise. */
 int32_t a2m_self_attention_eval_fits(int32_t C, int32_t T);
 int a2m_self_attention_eval_f32(const float* x, int64_t x_bs, int32_t B, int32_t C, int32_t T,

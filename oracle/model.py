@@ -91,7 +91,9 @@ def channel_attention(c, pfx, x):
     def mlp(z):
         z = F.relu(F.linear(z, c[pfx + '.fc.0.weight'], c[pfx + '.fc.0.bias']))
         return torch.sigmoid(F.linear(z, c[pfx + '.fc.2.weight'], c[pfx + '.fc.2.bias']))
-    return x * (mlp(x.mean(-1)) + mlp(x.amax(-1))).unsqueeze(-1)
+    # adaptive_max_pool1d, as the reference layer: its backward sends a tie's whole gradient to the
+    # first maximum (amax splits it evenly)
+    return x * (mlp(x.mean(-1)) + mlp(F.adaptive_max_pool1d(x, 1).squeeze(-1))).unsqueeze(-1)
 
 
 def res_block(c, pfx, x):

@@ -218,10 +218,11 @@ def test_interp_time():
                                    (3, 128, 36), (2, 2048, 32), (3, 2048, 4), (2, 512, 12), (4, 2048, 20)])
 def test_self_attention(B, C, T):
     """Eval path: (B, 256, 64) / (B, 128, 36) run the fused QKV + attention kernel
-    (a2m_self_attention_eval_f32); C = 2048 / 512 at T <= 32 the wide attention core
-    (attn_core_wide_kernel, the UNet's and D's SelfAttention(2048)); the others the packed
-    QKV GEMM + core / general path.  The attention matrix kept for the backward pass is
-    checked against Q^T K softmax on the host."""
+    (a2m_self_attention_eval_f32); C = 2048 at T in {4, 16, 20, 32} the wide attention core
+    (attn_core_wide_kernel, the UNet's and D's SelfAttention(2048)); C = 512 at T = 12 the
+    attention core (attn_core_kernel: C/8 = 64 fits it, and it is asked first); (1, 64, 480) and
+    (3, 16, 5) the general path (a2m_self_attention_route tells which).  The attention matrix kept
+    for the backward pass is checked against Q^T K softmax on the host."""
     from a2m import functional as F
     from oracle import model as OM
     x, res = _rand(B, C, T, seed=50), _rand(B, C, T, seed=51)
