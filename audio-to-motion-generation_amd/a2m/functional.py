@@ -105,11 +105,75 @@ def conv1d_tap_packed(w, cache=None):
     return packed, chunk
 
 
-def conv1d(x, w, b=None, stride=1, pad=0, bn=None, act=ACT_NONE, slope=0.2, out=None, cache=None):
+ROUTE_WINO = 16   # flags bit of a2m_conv1d_wino_route: the launch takes the Winograd F(2,3) tile
+
+
+def conv1d_wino_packed(w, cache=None):
+    """Winograd F(2,3) points of 3-tap conv1d weights, [Co][Ci/32][4][32]
+    (a2m_conv1d_wino_pack_f32), cached in `cache` per weight version under its own key."""
+    key = _wkey((w,)) + ('wino',)
+    if cache is not None and cache.get('wino_key') == key:
+        return cache['wino_w']
+    Co, Ci, ks = w.shape
+    assert ks == 3
+    packed = torch.empty(Co * Ci * 4, device=w.device)
+    N.check(N.lib.a2m_conv1d_wino_pack_f32(_p(w), Co, Ci, _p(packed), _stream()))
+    if cache is not None:
+        cache.update(wino_key=key, wino_w=packed)
+    return packed
+
+
+def conv1d_wino_route(x, Co, out, wino=True, G=1, xs_g=0, ys_g=0):
+    """The engine's route for the 3-tap pad-1 conv1d of x [B, Ci, T] into out, with or without the
+    Winograd request (a2m_conv1d_wino_route; no launch): dict of kind, tile, bk, splits, kchunk,
+    ma, mb, flags (flags & ROUTE_WINO: Winograd tile).  None where the operands fit neither tap
+    path or the library has no Winograd entry."""
+    B, Ci, T = x.shape
+    if not hasattr(N.lib, 'a2m_conv1d_wino_route') or not _tap_eligible(x, 3, 1, 1, Ci):
+        return None
+    xsb, ysb = (T * x.stride(2), T * out.stride(2)) if B == 1 else (x.stride(0), out.stride(0))
+    o = (ctypes.c_int32 * 8)()
+    rc = N.lib.a2m_conv1d_wino_route(_p(x), xs_g, xsb, x.stride(1), G, B, Ci, T, _p(x), Co, None, _p(out), ys_g,
+                                     ysb, out.stride(1), out.stride(2), 1 if wino else 0, o)
+    if rc != 0:
+        return None
+    return dict(zip(('kind', 'tile', 'bk', 'splits', 'kchunk', 'ma', 'mb', 'flags'), o))
+
+
+def _wino_taken(x, Co, out, **kw):
+    r = conv1d_wino_route(x, Co, out, True, **kw)
+    return r is not None and bool(r['flags'] & ROUTE_WINO)
+
+
+def conv1d_wino(x, w, b=None, bn=None, act=ACT_NONE, slope=0.2, out=None, cache=None, res=None):
+    """3-tap pad-1 stride-1 conv1d on the Winograd F(2,3) tile (a2m_conv1d_wino_fwd_f32); raises
+    where the engine refuses it (see conv1d(wino=True) for the request with a fallback).  res: a
+    residual added after the activation, addressed like out (same shape and strides)."""
+    _check_dev(x, w, b, out, res)
+    B, Ci, T = x.shape
+    Co = w.shape[0]
+    assert w.shape[1:] == (Ci, 3) and w.is_contiguous() and x.stride(2) == 1
+    if out is None:
+        out = torch.empty(B, Co, T, device=x.device, dtype=x.dtype)
+    assert tuple(out.shape) == (B, Co, T)
+    assert res is None or (res.shape == out.shape and res.stride() == out.stride())
+    xs, ys = list(x.stride()), list(out.stride())
+    if B == 1:
+        xs[0], ys[0] = T * xs[2], T * ys[2]
+    packed = conv1d_wino_packed(w, cache)
+    _with_ws(x.device, lambda wp, wn: N.lib.a2m_conv1d_wino_fwd_f32(
+        _p(x), xs[0], xs[1], B, Ci, T, _p(packed), _p(b), Co, *_bn_args(bn), act, slope, _p(res), _p(out),
+        ys[0], ys[1], ys[2], wp, wn, _stream()))
+    return out
+
+
+def conv1d(x, w, b=None, stride=1, pad=0, bn=None, act=ACT_NONE, slope=0.2, out=None, cache=None, wino=False):
     """x: [B, Ci, Tin] (any strides), w: [Co, Ci, k] (or [Co, Ci] for a linear / 1x1).
     Returns / fills out [B, Co, Tout] (any strides).  With `cache` (a dict owned by the module),
     stride-1 same-padded convs over clips that tile the GEMM's 64 rows run on the tap-chunked
-    path (a2m_conv1d_tap_fwd_f32: no im2col matrix; packed weights kept in `cache`)."""
+    path (a2m_conv1d_tap_fwd_f32: no im2col matrix; packed weights kept in `cache`).  wino=True
+    (with `cache`) asks for the Winograd F(2,3) tile; where the engine refuses it (shape, bf16
+    precision, a per-shape rule) the call takes exactly the path of wino=False."""
     _check_dev(x, w, b, out)
     B, Ci, Tin = x.shape
     Co, ks = w.shape[0], (w.shape[2] if w.dim() == 3 else 1)
@@ -121,6 +185,8 @@ def conv1d(x, w, b=None, stride=1, pad=0, bn=None, act=ACT_NONE, slope=0.2, out=
     xs, ys = list(x.stride()), list(out.stride())
     if B == 1:  # batch stride is irrelevant; make single-batch row views look uniform
         xs[0], ys[0] = Tin * xs[2], Tout * ys[2]
+    if wino and cache is not None and ks == 3 and stride == 1 and pad == 1 and _wino_taken(x, Co, out):
+        return conv1d_wino(x, w, b, bn, act, slope, out, cache)
     if cache is not None and _tap_eligible(x, ks, stride, pad, Ci) and \
             Ci % N.lib.a2m_conv1d_tap_chunk() == 0:
         packed, chunk = conv1d_tap_packed(w, cache)
@@ -165,6 +231,30 @@ def conv1d_tap_group(xs, packed, chunk, bias, Co, ks, pad, bn, act, slope, outs)
         _p(x0), xs_g, xsb, x0.stride(1), G, B, Ci, T, _p(packed), packed.stride(0), chunk, _p(bias), Co,
         ks, pad, *_bn_args(bn), act, slope, _p(y0), ys_g, ysb, y0.stride(1), y0.stride(2), wp, wn,
         _stream()))
+    return outs
+
+
+def conv1d_wino_group_taken(xs, Co, outs):
+    """Whether the grouped launch of these operands takes the Winograd tile on request."""
+    return _wino_taken(xs[0], Co, outs[0], G=len(xs), xs_g=_group_stride(xs), ys_g=_group_stride(outs))
+
+
+def conv1d_wino_group(xs, packed, bias, Co, bn, act, slope, outs):
+    """conv1d_tap_group on the Winograd F(2,3) tile (a2m_conv1d_wino_group_fwd_f32): packed [G, n]
+    stacks each problem's conv1d_wino_packed weights."""
+    x0, y0 = xs[0], outs[0]
+    _check_dev(x0, y0, packed)
+    B, Ci, T = x0.shape
+    assert all(x.stride() == x0.stride() and x.shape == x0.shape for x in xs)
+    assert all(y.stride() == y0.stride() and tuple(y.shape) == (B, Co, T) for y in outs)
+    G = len(xs)
+    xs_g, ys_g = _group_stride(xs), _group_stride(outs)
+    xsb, ysb = x0.stride(0), y0.stride(0)
+    if B == 1:
+        xsb, ysb = T * x0.stride(2), T * y0.stride(2)
+    _with_ws(x0.device, lambda wp, wn: N.lib.a2m_conv1d_wino_group_fwd_f32(
+        _p(x0), xs_g, xsb, x0.stride(1), G, B, Ci, T, _p(packed), packed.stride(0), _p(bias), Co,
+        *_bn_args(bn), act, slope, None, _p(y0), ys_g, ysb, y0.stride(1), y0.stride(2), wp, wn, _stream()))
     return outs
 
 

@@ -15,12 +15,18 @@ folded into the GEMM epilogue, zero-copy skip concatenation, dead encoder column
 pruned).  In training mode they run through a2m.autograd, whose Functions pair the same
 forward kernels with hand-written HIP backward kernels.
 """
+import os
+
 import torch
 import torch.nn as nn
 
 from . import functional as F
 
 ACT = {'relu': F.ACT_RELU, 'lrelu': F.ACT_LRELU}
+# the eval forwards of the stride-1 3-tap 1-D convs (ConvNormRelu, so ResBlock and the UNet too; also
+# the grouped decoder launches) ask the engine for the Winograd F(2,3) tile; the engine's route
+# takes it per shape (csrc/gemm_route.cpp) or runs the direct tap tile.  Training never asks.
+_WINO = os.environ.get('A2M_WINO', '1') != '0'
 
 
 def _grad_path(module, *tensors):
@@ -119,7 +125,7 @@ class ConvNormRelu(nn.Module):
         k, s, p = self.geometry()
         if self.type == '1d':
             return F.conv1d(x, self.conv.weight, self.conv.bias, s, p, bn=self.bn_eval(),
-                            act=self.act, out=out, cache=self._tap)
+                            act=self.act, out=out, cache=self._tap, wino=_WINO)
         return F.conv2d(x, self.conv.weight, self.conv.bias, s, tuple(p), bn=self.bn_eval(),
                         act=self.act, cols=cols, out=out)
 

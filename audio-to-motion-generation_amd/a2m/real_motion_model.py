@@ -12,6 +12,7 @@ import torch
 import torch.nn as nn
 
 from . import functional as F
+from . import model_layers as ML
 from . import skeleton as S
 from .graph_layers import GATConv, GraphConv
 from .model_layers import (AudioEncoder, ChannelAttention, ConvNormRelu, ResBlock, SelfAttention,
@@ -172,17 +173,28 @@ class SelfAttention_G(_GraphTopology):
         return c[1]
 
     def _cnr_group(self, key, mods, xs, outs):
-        def build(ms):
-            chunk = N_tap_chunk()
-            packed = torch.stack([F.conv1d_tap_packed(m.conv.weight, m._tap)[0] for m in ms])
+        def params(ms):
             st = lambda f: torch.stack([f(m) for m in ms]).contiguous()
             bn = (st(lambda m: m.norm.weight), st(lambda m: m.norm.bias),
                   st(lambda m: m.norm.running_mean), st(lambda m: m.norm.running_var), ms[0].norm.eps)
-            return packed, chunk, st(lambda m: m.conv.bias), bn
-        packed, chunk, bias, bn = self._group(key, mods, build)
+            return st(lambda m: m.conv.bias), bn
+
+        def build(ms):
+            chunk = N_tap_chunk()
+            packed = torch.stack([F.conv1d_tap_packed(m.conv.weight, m._tap)[0] for m in ms])
+            return (packed, chunk) + params(ms)
         m0 = mods[0]
         k, s, p = m0.geometry()
-        F.conv1d_tap_group(xs, packed, chunk, bias, m0.conv.out_channels, k, p, bn, m0.act, 0.2, outs)
+        Co = m0.conv.out_channels
+        if ML._WINO and (k, s, p) == (3, 1, 1) and F.conv1d_wino_group_taken(xs, Co, outs):
+            # the request of the per-branch schedule (ConvNormRelu.forward): both schedules run the same tile
+            def build_wino(ms):
+                return (torch.stack([F.conv1d_wino_packed(m.conv.weight, m._tap) for m in ms]),) + params(ms)
+            packed, bias, bn = self._group(key + '.wino', mods, build_wino)
+            F.conv1d_wino_group(xs, packed, bias, Co, bn, m0.act, 0.2, outs)
+            return outs
+        packed, chunk, bias, bn = self._group(key, mods, build)
+        F.conv1d_tap_group(xs, packed, chunk, bias, Co, k, p, bn, m0.act, 0.2, outs)
         return outs
 
     def _sa_group(self, key, mods, xs, outs, res=None):

@@ -737,5 +737,8 @@ __global__ __launch_bounds__(256) void gemm_pipe_kernel_pair(GemmArgs a0, GemmAr
 bool launch_pipe(const GemmArgs& a, int mb, int nt, int ma, int batch, hipStream_t st);
 // gemm_f32_pipe_pair.hip: per-tap problems of nt0 and nt1 taps (1-3 each)
 void launch_pipe_pair(const GemmArgs& a0, const GemmArgs& a1, int nt0, int nt1, hipStream_t st);
+// gemm_f32_pipe_wino.hip: the Winograd F(2,3) tile of the halo layout's problem class (a.A: the
+// weights packed by a2m_conv1d_wino_pack_f32, a.K and the split bounds those of the direct conv)
+void launch_pipe_wino(const GemmArgs& a, int batch, hipStream_t st);
 
 }  // namespace a2m

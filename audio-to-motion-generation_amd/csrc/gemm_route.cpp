@@ -315,6 +315,27 @@ static PipeOperands pipe_operands(const Gather& A, const Gather& B, int ma, int 
   return {false, false, 0, 0};
 }
 
+// Shape classes of requested, eligible launches that stay on the direct tile because it measured
+// faster there: blocks = 64x64 tiles x batch of the launch (before split-K), K = 3 Ci.  A launch
+// outside every class takes the Winograd tile.  The table is empty: all six shapes of the bench
+// step measured faster on the Winograd tile, alone and in the step's kernel trace -- the UNet's
+// five (512-1024 blocks, K 768-6144) by 9-19 %, the decoders' one-block-per-CU launch (256 blocks,
+// K 768) by 5 % alone and 11 % in the trace (profiles/wino_conv.txt).
+struct WinoDirectRule {
+  int64_t min_blocks, max_blocks;
+  int min_k, max_k;
+};
+static const std::vector<WinoDirectRule> kWinoDirect = {};
+bool wino_rule(int M, int N, int K, int batch) {
+  const int64_t blocks = cdiv(M, 64) * cdiv(N, 64) * (int64_t)batch;
+  // experiments: launches of fewer blocks stay on the direct tile (read once, like A2M_GEMM_PLAN_RULES)
+  static const int min_blocks = env_int("A2M_WINO_MIN_BLOCKS", 0);
+  if (blocks < min_blocks) return false;
+  for (const WinoDirectRule& d : kWinoDirect)
+    if (blocks >= d.min_blocks && blocks <= d.max_blocks && K >= d.min_k && K <= d.max_k) return false;
+  return true;
+}
+
 GemmRoute gemm_route(const Gather& A, const Gather& B, const Epilogue& E, int M, int N, int K, int batch,
                      int force_split, const RouteConfig& cfg) {
   GemmRoute r{};
@@ -350,6 +371,13 @@ GemmRoute gemm_route(const Gather& A, const Gather& B, const Epilogue& E, int M,
   r.mcontig = E.som == 1 && M > 1 && !r.interp;
   r.vec4 = epi_vec4(E, N, r.mcontig, r.reduce);
   r.ks = 1;
+  // the Winograd F(2,3) tile (gemm_f32_pipe_wino.hip), on request only: the fp32 pipelined tile's
+  // halo-layout launches (3 taps, pad 1, clips of T >= 16) with whole 32-channel chunks and dense
+  // packed weights of 4 Ci floats a row, where the rule table keeps the shape on it.  The plan
+  // (tile, splits, kchunk) is the direct conv's.  Refused: exactly the route without the request.
+  r.wino = cfg.wino && pipe && prec == 0 && r.halo && po.ma == 0 && K % 96 == 0 && !r.interp &&
+           A.sr0 == 4 * (K / 3) && pipe_below((int64_t)(M - 1) * A.sr0 + 4 * (K / 3)) &&
+           wino_rule(M, N, K, batch);
   if (pipe) {
     r.kind = A2M_GEMM_KIND_PIPE;
     r.pipe_mb = po.mb; r.pipe_ma = po.ma;

@@ -13,6 +13,7 @@ struct RouteConfig {
   int pair_override;    // a2m_convt_pair_override: -1 default (gemm_pair's fill rule), 0 never, 1 whenever eligible
   int override_tile, override_split;   // a2m_gemm_plan_override (tuning)
   int halo_on;          // A2M_GEMM_HALO
+  int wino;             // this launch asks for the Winograd F(2,3) tile (a2m_conv1d_wino_*; not process-wide)
 };
 
 struct GemmRoute {
@@ -22,6 +23,7 @@ struct GemmRoute {
   int pipe_mb, pipe_nt, pipe_ma;   // template arguments of the pipelined kernel (kind PIPE)
   int ks;                     // gemm_tile wave groups (1 or 2)
   bool halo, vec4, mcontig, reduce, interp;
+  bool wino;                  // kind PIPE as gemm_pipe_kernel_wino: A is the Winograd-packed weights
 };
 
 // Pure: no HIP call, no allocation, no mutable file-scope state (A2M_GEMM_PLAN_RULES is parsed
@@ -38,5 +40,8 @@ size_t split_ws_bytes(const GemmRoute& r, int M, int N, int batch);
 size_t gemm_ws_bytes(int M, int N, int K, int batch, const RouteConfig& cfg);
 // whether A2M_GEMM_PLAN_RULES fixes more than one split for the shape
 bool plan_rule_splits(int M, int N, int K);
+// whether the per-shape rule table keeps a requested, eligible launch on the Winograd tile (false:
+// the direct tile measured faster for the shape class)
+bool wino_rule(int M, int N, int K, int batch);
 
 }  // namespace a2m

@@ -7,6 +7,7 @@
 #include <cstdlib>
 
 #include "a2m_internal.h"
+#include "gemm_route.h"
 
 namespace a2m {
 
@@ -399,6 +400,22 @@ __global__ void conv1d_tap_pack_kernel(const float* w, int Co, int Ci, int ks, i
   }
 }
 
+// 3-tap Conv1d weights [Co][Ci][3] -> Winograd F(2,3) points [Co][Ci/32][4][32]:
+// U0 = g0, U1 = (g0 + g1 + g2) / 2, U2 = (g0 - g1 + g2) / 2, U3 = g2
+__global__ void conv1d_wino_pack_kernel(const float* w, int Co, int Ci, float* out) {
+  const int64_t total = (int64_t)Co * Ci;
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < total;
+       i += (int64_t)gridDim.x * blockDim.x) {
+    const int ci = (int)(i % Ci), co = (int)(i / Ci);
+    const float g0 = w[3 * i], g1 = w[3 * i + 1], g2 = w[3 * i + 2];
+    float* const o = out + (((int64_t)co * (Ci / 32) + ci / 32) * 4) * 32 + ci % 32;
+    o[0] = g0;
+    o[32] = ((g0 + g2) + g1) * 0.5f;
+    o[64] = ((g0 + g2) - g1) * 0.5f;
+    o[96] = g2;
+  }
+}
+
 // [wq; wk; wv] -> wcat [C/4 + C][C], biases -> bcat (zeros where a bias pointer is NULL)
 __global__ void stack_qkv_kernel(const float* wq, const float* bq, const float* wk, const float* bk,
                                  const float* wv, const float* bv, int C, float* wcat, float* bcat) {
@@ -747,6 +764,98 @@ int a2m_conv1d_tap_group_fwd_f32(const float* x, int64_t xs_g, int64_t xs_b, int
   E.N1 = 1; E.N2 = T; E.so0 = (int)ys_b; E.so1 = 0; E.so2 = (int)ys_t; E.som = (int)ys_c;
   E.bstride = ys_g; E.pstride = Co;
   return gemm(A, Bg, E, Co, B * T, Ci * ks, G, ws, ws_bytes, as_stream(stream));
+}
+
+int a2m_conv1d_wino_pack_f32(const float* w, int32_t Co, int32_t Ci, float* packed, void* stream) {
+  A2M_CHECK_ARG(w && packed && Co > 0 && Ci > 0 && Ci % 32 == 0, "conv1d_wino_pack: bad args Co=%d Ci=%d (Ci %% 32)",
+                Co, Ci);
+  A2M_CHECK_ARG(fits32((int64_t)Co * Ci * 4), "conv1d_wino_pack: too large");
+  hipLaunchKernelGGL(conv1d_wino_pack_kernel, dim3((unsigned)std::min<int64_t>(cdiv((int64_t)Co * Ci, 256), 8192)),
+                     dim3(256), 0, as_stream(stream), w, Co, Ci, packed);
+  A2M_LAUNCH_CHECK();
+  return A2M_OK;
+}
+
+// the operands of a 3-tap pad-1 stride-1 conv1d over G problems as the engine sees them: A the
+// packed weights (wino: 4 Ci floats a row, else the tap-chunked 3 Ci), B the tap conv of x
+struct WinoProblem {
+  Gather A, B;
+  Epilogue E;
+};
+static int wino_problem(WinoProblem& p, const float* x, int64_t xs_g, int64_t xs_b, int64_t xs_c, int32_t G,
+                        int32_t B, int32_t Ci, int32_t T, const float* packed, int64_t w_gs, int32_t wino,
+                        const float* bias, int32_t Co, const float* bn_w, const float* bn_b, const float* bn_rm,
+                        const float* bn_rv, float bn_eps, int32_t act, float slope, const float* res, float* y,
+                        int64_t ys_g, int64_t ys_b, int64_t ys_c, int64_t ys_t) {
+  A2M_CHECK_ARG(x && packed && y && G > 0, "conv1d_wino: null pointer / G=%d", G);
+  A2M_CHECK_ARG(B > 0 && Ci > 0 && Co > 0 && T > 0, "conv1d_wino: bad shape B=%d Ci=%d Co=%d T=%d", B, Ci, Co, T);
+  const int kw = wino ? 4 : 3;
+  A2M_CHECK_ARG(fits32(xs_b) && fits32(xs_c) && fits32((int64_t)B * xs_b) && fits32((int64_t)B * ys_b) &&
+                    fits32(ys_c) && fits32(ys_t) && fits32((int64_t)Co * Ci * kw) &&
+                    (G == 1 || (ys_g != 0 && w_gs >= (int64_t)Co * Ci * kw)),
+                "conv1d_wino: strides");
+  A2M_CHECK_ARG((reinterpret_cast<uintptr_t>(x) % 16) == 0 && xs_b % 4 == 0 && xs_c % 4 == 0 && xs_g % 4 == 0 &&
+                    w_gs % 4 == 0 && (reinterpret_cast<uintptr_t>(packed) % 16) == 0,
+                "conv1d_wino: x rows / packed weights must be 16-byte aligned");
+  p.A = dense_rk(packed, Ci * kw, w_gs);
+  Gather Bg{};
+  Bg.base = x; Bg.bstride = xs_g;
+  Bg.sr0 = (int)xs_b; Bg.R1 = 1; Bg.R2 = T; Bg.sk0 = (int)xs_c;
+  Bg.K1 = Bg.K2 = 1; Bg.divh = Bg.divw = 1; Bg.Lh = Bg.Lw = 1;
+  Bg.cw = -1; Bg.tapconv = 3;
+  p.B = Bg;
+  Epilogue E = epi_bn(y, bias, bn_w, bn_b, bn_rm, bn_rv, bn_eps, act, slope);
+  E.N1 = 1; E.N2 = T; E.so0 = (int)ys_b; E.so1 = 0; E.so2 = (int)ys_t; E.som = (int)ys_c;
+  E.bstride = ys_g; E.pstride = Co;
+  E.res1 = res;
+  p.E = E;
+  return A2M_OK;
+}
+
+int a2m_conv1d_wino_route(const float* x, int64_t xs_g, int64_t xs_b, int64_t xs_c, int32_t G, int32_t B,
+                          int32_t Ci, int32_t T, const float* packed, int32_t Co, const float* res, float* y,
+                          int64_t ys_g, int64_t ys_b, int64_t ys_c, int64_t ys_t, int32_t wino, int32_t out[8]) {
+  A2M_CHECK_ARG(out != nullptr, "conv1d_wino_route: null out");
+  WinoProblem p;
+  const int rc = wino_problem(p, x, xs_g, xs_b, xs_c, G, B, Ci, T, packed, (int64_t)Co * Ci * 4, wino, nullptr, Co,
+                              nullptr, nullptr, nullptr, nullptr, 1e-5f, 0, 0.2f, res, y, ys_g, ys_b, ys_c, ys_t);
+  if (rc != A2M_OK) return rc;
+  RouteConfig cfg = route_config();
+  cfg.wino = wino;
+  const GemmRoute r = gemm_route(p.A, p.B, p.E, Co, B * T, 3 * Ci, G, 0, cfg);
+  const int32_t o[8] = {r.kind, r.tile, r.bk, r.splits, r.kchunk, r.ma, r.mb,
+                        (r.vec4 ? 1 : 0) | (r.mcontig ? 2 : 0) | (r.halo ? 4 : 0) | (r.reduce ? 8 : 0) |
+                            (r.wino ? 16 : 0)};
+  for (int i = 0; i < 8; ++i) out[i] = o[i];
+  return A2M_OK;
+}
+
+int a2m_conv1d_wino_group_fwd_f32(const float* x, int64_t xs_g, int64_t xs_b, int64_t xs_c, int32_t G,
+                                  int32_t B, int32_t Ci, int32_t T, const float* packed, int64_t w_gs,
+                                  const float* bias, int32_t Co, const float* bn_w, const float* bn_b,
+                                  const float* bn_rm, const float* bn_rv, float bn_eps, int32_t act,
+                                  float slope, const float* res, float* y, int64_t ys_g, int64_t ys_b,
+                                  int64_t ys_c, int64_t ys_t, void* ws, size_t ws_bytes, void* stream) {
+  WinoProblem p;
+  const int rc = wino_problem(p, x, xs_g, xs_b, xs_c, G, B, Ci, T, packed, w_gs, 1, bias, Co, bn_w, bn_b, bn_rm,
+                              bn_rv, bn_eps, act, slope, res, y, ys_g, ys_b, ys_c, ys_t);
+  if (rc != A2M_OK) return rc;
+  RouteConfig cfg = route_config();
+  cfg.wino = 1;
+  A2M_CHECK_ARG(gemm_route(p.A, p.B, p.E, Co, B * T, 3 * Ci, G, 0, cfg).wino,
+                "conv1d_wino: not a Winograd launch (fp32, T >= 16 with 64 %% T == 0, Ci %% 32 == 0, and a shape "
+                "the rule table keeps on it): B=%d Ci=%d Co=%d T=%d G=%d precision %d",
+                B, Ci, Co, T, G, cfg.prec);
+  return gemm(p.A, p.B, p.E, Co, B * T, 3 * Ci, G, ws, ws_bytes, as_stream(stream), 0, 1);
+}
+
+int a2m_conv1d_wino_fwd_f32(const float* x, int64_t xs_b, int64_t xs_c, int32_t B, int32_t Ci, int32_t T,
+                            const float* packed, const float* bias, int32_t Co, const float* bn_w,
+                            const float* bn_b, const float* bn_rm, const float* bn_rv, float bn_eps,
+                            int32_t act, float slope, const float* res, float* y, int64_t ys_b, int64_t ys_c,
+                            int64_t ys_t, void* ws, size_t ws_bytes, void* stream) {
+  return a2m_conv1d_wino_group_fwd_f32(x, 0, xs_b, xs_c, 1, B, Ci, T, packed, 0, bias, Co, bn_w, bn_b, bn_rm, bn_rv,
+                                       bn_eps, act, slope, res, y, 0, ys_b, ys_c, ys_t, ws, ws_bytes, stream);
 }
 
 int a2m_convt1d_pack_f32(const float* w, int32_t Ci, int32_t Co, int32_t ks, int32_t stride,

@@ -181,6 +181,34 @@ int a2m_conv1d_tap_group_fwd_f32(const float* x, int64_t xs_g, int64_t xs_b, int
                                  const float* bn_rv, float bn_eps, int32_t act, float slope, float* y,
                                  int64_t ys_g, int64_t ys_b, int64_t ys_c, int64_t ys_t, void* ws,
                                  size_t ws_bytes, void* stream);
+/* Winograd F(2,3) form of the 3-tap, pad-1, stride-1 conv1d (opt-in; a2m_conv1d_tap_fwd_f32 is
+ * unchanged): two outputs of a clip from 4 multiplies per input channel instead of 6, fp32 only.
+ * Weights [Co][Ci][3] are packed once per weight version by a2m_conv1d_wino_pack_f32 as
+ * [Co][Ci/32][4][32] (Co*Ci*4 floats): U0 = g0, U1 = (g0+g1+g2)/2, U2 = (g0-g1+g2)/2, U3 = g2.
+ * Eligible: fp32 precision, clips of T >= 16 with 64 % T == 0, Ci % 32 == 0, x as for
+ * a2m_conv1d_tap_fwd_f32, and a shape the engine's per-shape rule table keeps on the Winograd
+ * tile.  The forwards return A2M_EINVAL ("conv1d_wino: not a Winograd launch ...") otherwise;
+ * a2m_conv1d_wino_route answers beforehand without launching: out as a2m_gemm_f32_route's, flags
+ * bit 4 set where the launch takes the Winograd tile.  With wino = 0 it is the route of the
+ * direct tap path (`packed` then stands for the tap-chunked weights), which is also what a
+ * refused request gets.  res (may be NULL): a residual added after the activation, addressed
+ * like y.  The group entry runs G problems as a2m_conv1d_tap_group_fwd_f32 does (w_gs >=
+ * Co*Ci*4).  Epilogue and output strides as a2m_conv1d_fwd_f32. */
+int a2m_conv1d_wino_pack_f32(const float* w, int32_t Co, int32_t Ci, float* packed, void* stream);
+int a2m_conv1d_wino_route(const float* x, int64_t xs_g, int64_t xs_b, int64_t xs_c, int32_t G, int32_t B,
+                          int32_t Ci, int32_t T, const float* packed, int32_t Co, const float* res, float* y,
+                          int64_t ys_g, int64_t ys_b, int64_t ys_c, int64_t ys_t, int32_t wino, int32_t out[8]);
+int a2m_conv1d_wino_fwd_f32(const float* x, int64_t xs_b, int64_t xs_c, int32_t B, int32_t Ci, int32_t T,
+                            const float* packed, const float* bias, int32_t Co, const float* bn_w,
+                            const float* bn_b, const float* bn_rm, const float* bn_rv, float bn_eps,
+                            int32_t act, float slope, const float* res, float* y, int64_t ys_b, int64_t ys_c,
+                            int64_t ys_t, void* ws, size_t ws_bytes, void* stream);
+int a2m_conv1d_wino_group_fwd_f32(const float* x, int64_t xs_g, int64_t xs_b, int64_t xs_c, int32_t G,
+                                  int32_t B, int32_t Ci, int32_t T, const float* packed, int64_t w_gs,
+                                  const float* bias, int32_t Co, const float* bn_w, const float* bn_b,
+                                  const float* bn_rm, const float* bn_rv, float bn_eps, int32_t act,
+                                  float slope, const float* res, float* y, int64_t ys_g, int64_t ys_b,
+                                  int64_t ys_c, int64_t ys_t, void* ws, size_t ws_bytes, void* stream);
 /* The same split in two: the per-phase weight packing (packed: Ci*Co*k floats) and the
  * forward on packed weights (callers cache the packing while the weights are unchanged). */
 int a2m_convt1d_pack_f32(const float* w, int32_t Ci, int32_t Co, int32_t ks, int32_t stride,
