@@ -3,6 +3,8 @@
 Drop-in modules for the reference's real_motion_model / model_layers / mel_features call
 surface; all compute runs in liba2m_hip.so (include/a2m.h) through a2m.functional.
 Importing this package loads the native library and fails loudly if it is missing.
+a2m.video renders pose tracks to frames and YUV4MPEG2 files; a2m.inference.generate_track
+stitches a recording's windows into one track.
 """
 import torch  # noqa: F401  (loads the ROCm runtime the library links against first)
 

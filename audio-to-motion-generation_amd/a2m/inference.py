@@ -5,13 +5,16 @@
                                       normalised poses mapped back: pose * std + mean
   generate_from_wave(g, wave, sr, ...)  the same from a raw recording: PATS log_mel_512 windows
                                       (pats_audio.log_mel_512_windows) -> generate
+  generate_track(g, wave, sr, overlap, ...)  a whole recording to ONE track [F, 104]: windows
+                                      whose starts lie T - overlap pose frames apart, cross-faded
+                                      and de-normalised in one pass (a2m_track_blend_f32)
   planar_frames(pose)       :262-266  [B, T, 104] -> [B, T, 2, 52] (x row, y row) for plotting
 
   GraphedGenerator(g, ...)  HIP-graph replay of a fixed-shape eval forward (the serving loop
                             of :247-260 at a fixed batch): one graph per decoder branch, the
                             two branches on two streams joined by events
 
-Plotting and ffmpeg (:23-207) stay host-side reference code (out of scope).
+Plotting (:23-200) is a2m.video: a device rasteriser writing YUV4MPEG2, no matplotlib or ffmpeg.
 """
 import torch
 
@@ -58,6 +61,78 @@ def generate_from_wave(generator, wave, sr, starts=None, time=4.3, fs_new=15, au
     audio = log_mel_512_windows(wave, sr, auto if starts is None else starts, window, interval,
                                 audio_mean, audio_std, **mel_kwargs)
     return generate(generator, audio, pose_mean, pose_std)
+
+
+def blend_track(windows, overlap, pose_mean=None, pose_std=None, out=None):
+    """windows [n, T, Fd] (device) whose starts lie T - overlap frames apart -> one track
+    [(n-1)(T-overlap) + T, Fd]: linear cross-fade over each overlap (weights (j + 0.5)/overlap and
+    its complement), then * pose_std + pose_mean when given.  Frames of a single window are copied
+    bit for bit (or equal normalization.denormalize bit for bit)."""
+    from ._native import check, lib
+    F._check_dev(windows, pose_mean, pose_std, out)
+    if windows.dim() != 3:
+        raise ValueError(f'windows must be [n, T, Fd], got {tuple(windows.shape)}')
+    n, T, Fd = windows.shape
+    if not 0 <= overlap <= T // 2:
+        raise ValueError(f'overlap {overlap} outside [0, T/2 = {T // 2}]')
+    if (pose_mean is None) != (pose_std is None):
+        raise ValueError('pose_mean and pose_std come together')
+    windows = windows.contiguous()
+    frames = (n - 1) * (T - overlap) + T if n else 0
+    if out is None:
+        out = torch.empty(frames, Fd, device=windows.device)
+    elif tuple(out.shape) != (frames, Fd) or not out.is_contiguous():
+        raise ValueError(f'out must be a contiguous [{frames}, {Fd}] tensor')
+    if pose_mean is not None:
+        pose_mean, pose_std = pose_mean.to(windows.device).contiguous(), pose_std.to(windows.device).contiguous()
+        if pose_mean.numel() != Fd or pose_std.numel() != Fd:
+            raise ValueError(f'pose_mean and pose_std must have {Fd} entries')
+    check(lib.a2m_track_blend_f32(F._p(windows), n, T, Fd, int(overlap), F._p(pose_mean), F._p(pose_std),
+                                  F._p(out), F._stream()), value_error=True)
+    return out
+
+
+def track_starts(n_feature_frames, overlap=16, time=4.3, fs_new=15):
+    """Feature-frame starts k * (T - overlap) * interval of every window that fits into a
+    recording of n_feature_frames audio/log_mel_512 frames -> (starts int64, window, interval, T)."""
+    import numpy as np
+    from .windowing import window_index
+    _, window, interval = window_index(n_feature_frames, 'audio/log_mel_512', fs_new, time)
+    T = (window + interval - 1) // interval
+    if not 0 <= overlap <= T // 2:
+        raise ValueError(f'overlap {overlap} outside [0, T/2 = {T // 2}]')
+    if n_feature_frames < window:
+        raise ValueError(f'the recording has {n_feature_frames} feature frames; one window needs {window}')
+    step = (T - overlap) * interval
+    n = (n_feature_frames - window) // step + 1
+    return step * np.arange(n, dtype=np.int64), window, interval, T
+
+
+@torch.no_grad()
+def generate_track(generator, wave, sr, overlap=16, batch=64, time=4.3, fs_new=15, audio_mean=None,
+                   audio_std=None, pose_mean=None, pose_std=None, resample_to=None,
+                   res_type='kaiser_best', **mel_kwargs):
+    """A recording of any length to one continuous track: wave [S] (device) -> poses [F, 104].
+    generate_from_wave returns separate windows, which jump at every border when laid end to end;
+    here the windows start (T - overlap) pose frames apart (feature frame k * (T - overlap) *
+    interval, as many as fit; ValueError when not even one does), the generator runs on at most
+    `batch` of them per call, and a2m_track_blend_f32 cross-fades each overlap and applies
+    pose_mean / pose_std in one pass: F = (n - 1)(T - overlap) + T.  The other arguments are
+    generate_from_wave's.  overlap = 0 is the concatenation of generate_from_wave's windows."""
+    from .pats_audio import log_mel_512_windows, num_frames, resample
+    if batch < 1:
+        raise ValueError('batch must be >= 1')
+    if resample_to is not None:
+        wave, sr = resample(wave, sr, resample_to, res_type), resample_to
+    starts, window, interval, _ = track_starts(num_frames(wave.shape[-1], 2048, 512, True), overlap,
+                                               time, fs_new)
+    poses = []
+    for i in range(0, len(starts), batch):
+        audio = log_mel_512_windows(wave, sr, starts[i:i + batch], window, interval, audio_mean,
+                                    audio_std, **mel_kwargs)
+        poses.append(generate(generator, audio))
+    windows = poses[0] if len(poses) == 1 else torch.cat(poses)
+    return blend_track(windows, overlap, pose_mean, pose_std)
 
 
 def planar_frames(pose):

@@ -714,6 +714,50 @@ int a2m_window_gather_f32(const float* data, int64_t length, int32_t C, const in
                           int32_t n_windows, int32_t window, int32_t interval, const float* mean,
                           const float* std_, float* out, void* stream);
 
+/* ---- Pose video and track stitching ----
+ * a2m_render_poses_u8 stands in for the drawing of generate_motion_video.py:66-164
+ * (plot_head/body/hand_keypoints, draw_pose, draw_side_by_side_poses): every frame's P poses, each
+ * a set of L polylines over its K keypoints, drawn into planar uint8 frames out[N][3][H][W].
+ * kp [N][P][2][K] (x row, y row), xform [P][4] = sx, tx, sy, ty (px = sx*x + tx, py = sy*y + ty)
+ * and out are DEVICE pointers.  poly_idx (the keypoint indices of all polylines, concatenated),
+ * poly_off [L+1] (offsets into poly_idx, poly_off[0] = 0), poly_rgb [L][3] and bg [3] are HOST
+ * pointers: the tables are validated here (every polyline >= 2 indices, 0 <= index < K) and travel
+ * to the kernel by value, so the call allocates nothing, needs no workspace, is stream-ordered and
+ * can be captured in a HIP graph.  Limits: L <= A2M_RENDER_MAX_POLYLINES, poly_off[L] <=
+ * A2M_RENDER_MAX_INDICES, P*K <= A2M_RENDER_MAX_POINTS (the frame's keypoints are staged in LDS),
+ * P * ceil(poly_off[L] / 64) <= A2M_RENDER_MAX_CHUNKS (one culling mask per 64 segments of a pose).
+ * Pixel function: the centre of pixel (i, j) is (i + 0.5, j + 0.5); for one polyline of one pose d
+ * is the smallest distance from the centre to any of its segments (zero length: a point; a segment
+ * with a non-finite endpoint is skipped), its coverage c = clamp(half_width_px + 0.5 - d, 0, 1);
+ * per channel v = bg, then for p = 0..P-1, l = 0..L-1: v = v*(1 - c) + rgb[l]*c; the byte stored
+ * is (uint8)(v + 0.5f).  Blending is affine, so a palette and background converted to YCbCr give
+ * the Y, Cb and Cr planes of the same picture.  matplotlib's Agg output (butt caps, its own
+ * anti-aliasing) is NOT reproduced: the float64 restatement in tests/render_ref.py is the pin.
+ * A2M_EINVAL: a null pointer with N > 0; P, K, W or H < 1, L < 0; a polyline shorter than 2
+ * indices; an index outside [0, K); half_width_px negative or not finite; a limit exceeded.
+ * N = 0 returns A2M_OK without a launch and accepts NULL pointers. */
+#define A2M_RENDER_MAX_POLYLINES 128
+#define A2M_RENDER_MAX_INDICES 512
+#define A2M_RENDER_MAX_POINTS 4096
+#define A2M_RENDER_MAX_CHUNKS 1024
+int a2m_render_poses_u8(const float* kp, int32_t N, int32_t P, int32_t K, const int32_t* poly_idx,
+                        const int32_t* poly_off, const uint8_t* poly_rgb, int32_t L,
+                        const float* xform, float half_width_px, const uint8_t bg[3], int32_t W,
+                        int32_t H, uint8_t* out, void* stream);
+
+/* a2m_track_blend_f32 stitches the windows that generate_motion_video.py:247-260 produces one
+ * batch at a time into one track, de-normalising (:259-260) in the same pass.  win [n][T][Fd] are
+ * windows whose starts lie h = T - overlap frames apart (0 <= overlap <= T/2); out
+ * [(n-1)*h + T][Fd].  Gather form: an output frame reads one window, or two inside an overlap,
+ * where frame j of window k weighs (j + 0.5)/overlap at its head (k > 0, j < overlap) and
+ * (T - j - 0.5)/overlap at its tail (k < n-1, j >= T - overlap): the two weights sum to 1.
+ * out = sum w*win, then *std + mean when given (both or neither, [Fd]).  A frame of a single
+ * window is copied bit for bit, or equals a2m_pose_denormalize_f32 bit for bit; overlap = 0 is a
+ * concatenation.  No atomics: deterministic.  A2M_EINVAL: T or Fd < 1, n < 0, overlap out of
+ * range, one of mean / std alone, null win or out with n > 0.  n = 0 returns A2M_OK. */
+int a2m_track_blend_f32(const float* win, int32_t n, int32_t T, int32_t Fd, int32_t overlap,
+                        const float* mean, const float* std_, float* out, void* stream);
+
 /* Measurement hook (bench.py): while enabled, every launch of the implicit-GEMM engine (up to
  * 1024 per window; more make _read fail) carries a record of span stamps that its tile kernel and
  * split-K reduce write themselves (earliest block start, latest wave end on the GPU's constant-rate
