@@ -3,8 +3,9 @@
 Drop-in modules for the reference's real_motion_model / model_layers / mel_features call
 surface; all compute runs in liba2m_hip.so (include/a2m.h) through a2m.functional.
 Importing this package loads the native library and fails loudly if it is missing.
-a2m.video renders pose tracks to frames and YUV4MPEG2 files; a2m.inference.generate_track
-stitches a recording's windows into one track.
+a2m.video renders pose tracks to frames and YUV4MPEG2 files, or through a2m.jpeg (baseline JPEG
+on the device) and a2m.avi to Motion-JPEG AVI with sound; a2m.inference.generate_track stitches a
+recording's windows into one track and generate_video writes it as such a file.
 """
 import torch  # noqa: F401  (loads the ROCm runtime the library links against first)
 

@@ -160,6 +160,8 @@ SIGNATURES = {
     'a2m_window_gather_f32': (ctypes.c_int, [P, I64, I32, P, I32, I32, I32, P, P, P, P]),
     'a2m_render_poses_u8': (ctypes.c_int, [P, I32, I32, I32, P, P, P, I32, P, F32, P, I32, I32, P, P]),
     'a2m_track_blend_f32': (ctypes.c_int, [P, I32, I32, I32, I32, P, P, P, P]),
+    'a2m_jpeg_ws_bytes': (SZ, [I32, I32, I32]),
+    'a2m_jpeg_encode_u8': (ctypes.c_int, [P, I32, I32, I32, P, P, P, I64, P, P, SZ, P]),
     'a2m_gemm_timing_begin': (ctypes.c_int, []),
     'a2m_gemm_plan_override': (ctypes.c_int, [I32, I32]),
     'a2m_gemm_pipe_override': (ctypes.c_int, [I32]),

@@ -8,13 +8,16 @@
   generate_track(g, wave, sr, overlap, ...)  a whole recording to ONE track [F, 104]: windows
                                       whose starts lie T - overlap pose frames apart, cross-faded
                                       and de-normalised in one pass (a2m_track_blend_f32)
+  generate_video(g, wave, sr, fn, ...)  generate_track, drawn and written as a Motion-JPEG AVI
+                                      with the recording as its sound track (a2m.video)
   planar_frames(pose)       :262-266  [B, T, 104] -> [B, T, 2, 52] (x row, y row) for plotting
 
   GraphedGenerator(g, ...)  HIP-graph replay of a fixed-shape eval forward (the serving loop
                             of :247-260 at a fixed batch): one graph per decoder branch, the
                             two branches on two streams joined by events
 
-Plotting (:23-200) is a2m.video: a device rasteriser writing YUV4MPEG2, no matplotlib or ffmpeg.
+Plotting (:23-207) is a2m.video: a device rasteriser writing YUV4MPEG2 or, through the device JPEG
+encoder of a2m.jpeg, Motion-JPEG AVI with sound; no matplotlib or ffmpeg.
 """
 import torch
 
@@ -133,6 +136,20 @@ def generate_track(generator, wave, sr, overlap=16, batch=64, time=4.3, fs_new=1
         poses.append(generate(generator, audio))
     windows = poses[0] if len(poses) == 1 else torch.cat(poses)
     return blend_track(windows, overlap, pose_mean, pose_std)
+
+
+def generate_video(generator, wave, sr, output_fn, overlap=16, pose_mean=None, pose_std=None, quality=90,
+                   track_kwargs=None, **video_kwargs):
+    """A recording to a video with sound in one call: generate_track(generator, wave, sr, overlap,
+    pose_mean=, pose_std=, **track_kwargs) -> planar_frames -> a2m.video.save_pose_avi(track,
+    output_fn, wave, sr, quality, **video_kwargs), the same `wave` as the sound track (cut to the
+    picture's duration).  output_fn must end in .avi.  Returns the number of frames."""
+    from . import video
+    video._avi_name(output_fn)
+    track = generate_track(generator, wave, sr, overlap=overlap, pose_mean=pose_mean, pose_std=pose_std,
+                           **(track_kwargs or {}))
+    return video.save_pose_avi(planar_frames(track[None])[0], output_fn, wave=wave, sr=sr, quality=quality,
+                               **video_kwargs)
 
 
 def planar_frames(pose):

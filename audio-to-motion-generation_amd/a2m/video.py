@@ -6,6 +6,10 @@ generate_motion_video.py:23-200 over the a2m_render_poses_u8 rasteriser (csrc/re
   draw_side_by_side_poses(img, kp1, kp2, ...)     :139-164  one frame, two poses on one canvas
   save_side_by_side_video(tmp, kp1, kp2, fn, ...) :167-190  a YUV4MPEG2 file (no JPEGs, no ffmpeg)
   save_pose_video(keypoints, fn, ...)             the same for a single track
+  save_side_by_side_avi(kp1, kp2, fn, wave, sr)   the same as Motion-JPEG AVI with sound: frames
+  save_pose_avi(keypoints, fn, wave, sr, ...)     compressed on the device (a2m.jpeg, a2m.avi)
+  write_jpeg(path, frame, quality)                :174-185  one RGB frame as a .jpg file
+  save_video_from_audio_video(wav, avi, out)      :203-207  a .wav under the picture of an .avi
 
 What is drawn is the pixel function documented in include/a2m.h: round-capped polylines with a
 one-pixel linear edge.  matplotlib, PIL and ffmpeg are not used; parity with matplotlib's Agg
@@ -22,8 +26,10 @@ real topology instead: one two-point bone per joint of a2m.skeleton.Skeleton2D()
 import numpy as np
 import torch
 
+from . import avi, jpeg
 from . import functional as F
 from ._native import check, lib
+from .avi import save_video_from_audio_video  # noqa: F401  (generate_motion_video.py:203-207)
 from .skeleton import Skeleton2D
 
 PURPLE, GRAY, BLUE, RED, YELLOW = (128, 0, 128), (128, 128, 128), (0, 0, 255), (255, 0, 0), (255, 255, 0)
@@ -317,3 +323,95 @@ def save_pose_video(keypoints, output_fn, fps=FPS, chunk=64, polylines=REFERENCE
     _y4m_name(output_fn)
     return _write_video(output_fn, [_track(keypoints)[:, None]], polylines, colors, img_size, scale,
                         line_width, background, fps, chunk)
+
+
+# ------------------------------------------------------------------------------ JPEG and AVI
+def rgb_to_ycbcr_full(rgb):
+    """JFIF (BT.601 full-range) YCbCr bytes of RGB bytes [..., 3]: the twin of rgb_to_ycbcr for
+    the planes a JPEG holds."""
+    c = np.asarray(rgb, np.float64)
+    r, g, b = c[..., 0], c[..., 1], c[..., 2]
+    y = 0.299 * r + 0.587 * g + 0.114 * b
+    ycc = np.stack([y, 128 + (b - y) / 1.772, 128 + (r - y) / 1.402], -1)
+    return np.clip(np.floor(ycc + 0.5), 0, 255).astype(np.uint8)
+
+
+def write_jpeg(path, frame, quality=90):
+    """An RGB frame uint8 [3, H, W] (numpy or tensor), as draw_pose returns it -> a baseline JPEG
+    file (generate_motion_video.py:174-185 writes its %04d.jpg frames with matplotlib).  The
+    pixels are converted to full-range YCbCr on the host; the encoder runs on the device."""
+    fr = frame.cpu().numpy() if torch.is_tensor(frame) else np.asarray(frame)
+    if fr.ndim != 3 or fr.shape[0] != 3 or fr.dtype != np.uint8:
+        raise ValueError(f'frame must be uint8 [3, H, W], got {fr.dtype} {fr.shape}')
+    ycc = np.ascontiguousarray(rgb_to_ycbcr_full(fr.transpose(1, 2, 0)).transpose(2, 0, 1))
+    data = jpeg.encode_jpeg(torch.from_numpy(ycc)[None].cuda(), quality)[0]
+    with open(path, 'wb') as f:
+        f.write(data)
+
+
+def _avi_name(output_fn):
+    if not str(output_fn).endswith('.avi'):
+        raise ValueError(f'the video is written as Motion-JPEG AVI: output_fn must end in .avi, got {output_fn!r}')
+
+
+def _write_avi(output_fn, parts, wave, sr, quality, polylines, colors, canvas, scale, line_width, background,
+               fps, chunk):
+    """_write_video with the frames compressed on the device: each chunk is rendered with the
+    full-range YCbCr palette into one device buffer and encoded there; the offsets, then only
+    the compressed bytes (through one pinned buffer) cross to the host."""
+    if chunk < 1:
+        raise ValueError('chunk must be >= 1')
+    if (wave is None) != (sr is None):
+        raise ValueError('wave and sr come together')
+    ycc = rgb_to_ycbcr_full(np.asarray(_colors(polylines, colors), np.uint8).reshape(-1, 3))
+    bg = rgb_to_ycbcr_full(np.asarray(background, np.uint8))
+    W, H = int(round(canvas[0] * scale)), int(round(canvas[1] * scale))
+    qt = jpeg.quant_tables(quality)
+    pcm = None if wave is None else avi.pcm16(wave)
+    dev = None
+    with avi.AVIWriter(output_fn, W, H, fps, audio_rate=sr) as w:
+        header = jpeg.jpeg_header(W, H, qt)
+        if pcm is not None:
+            w.set_audio(pcm)
+        for part in parts:
+            for i in range(0, part.shape[0], chunk):
+                kp = part[i:i + chunk]
+                if dev is None or dev.shape[0] != kp.shape[0]:
+                    dev = torch.empty(kp.shape[0], 3, H, W, dtype=torch.uint8, device=kp.device)
+                render_poses(kp, polylines, ycc, canvas, scale, line_width, None, bg, out=dev)
+                buf, off = jpeg.encode_scans(dev, qt)
+                for n in range(kp.shape[0]):
+                    w.write_frame(header, buf[off[n]:off[n + 1]].data, jpeg.EOI)
+        return w.frames
+
+
+def save_side_by_side_avi(keypoints1, keypoints2, output_fn, wave=None, sr=None, quality=90, fps=FPS,
+                          chunk=64, polylines=REFERENCE_POLYLINES, colors=None, img_size=(3000, 1000),
+                          scale=0.5, line_width=None, background=(255, 255, 255)):
+    """save_side_by_side_video as a Motion-JPEG AVI, with `wave` (float [-1, 1], mono, at `sr`
+    samples a second; numpy or tensor) as its sound track, cut to the picture's duration.  The
+    frames are compressed on the device (a2m.jpeg); as in the reference, when keypoints2 is longer
+    by `diff` frames, the first `diff` frames show keypoints2 alone.  Returns the number of
+    frames."""
+    _avi_name(output_fn)
+    k1, k2 = _track(keypoints1), _track(keypoints2)
+    parts = []
+    diff = k2.shape[0] - k1.shape[0]
+    if diff > 0:
+        parts.append(k2[:diff, None])
+        k2 = k2[diff:]
+    n = k1.shape[0]
+    if k2.shape[0] < n:
+        raise ValueError(f'keypoints2 has {k2.shape[0]} frames, fewer than keypoints1 ({n})')
+    parts.append(torch.stack([k1, k2[:n]], 1))
+    return _write_avi(output_fn, parts, wave, sr, quality, polylines, colors, img_size, scale, line_width,
+                      background, fps, chunk)
+
+
+def save_pose_avi(keypoints, output_fn, wave=None, sr=None, quality=90, fps=FPS, chunk=64,
+                  polylines=REFERENCE_POLYLINES, colors=None, img_size=(3000, 1000), scale=0.5,
+                  line_width=None, background=(255, 255, 255)):
+    """One track [n, 2, K] -> a Motion-JPEG AVI with sound, as save_side_by_side_avi writes it."""
+    _avi_name(output_fn)
+    return _write_avi(output_fn, [_track(keypoints)[:, None]], wave, sr, quality, polylines, colors,
+                      img_size, scale, line_width, background, fps, chunk)

@@ -758,6 +758,66 @@ int a2m_render_poses_u8(const float* kp, int32_t N, int32_t P, int32_t K, const 
 int a2m_track_blend_f32(const float* win, int32_t n, int32_t T, int32_t Fd, int32_t overlap,
                         const float* mean, const float* std_, float* out, void* stream);
 
+/* ---- Baseline JPEG of rendered frames (generate_motion_video.py:174-185 writes %04d.jpg) ----
+ * a2m_jpeg_encode_u8 turns frames [N][3][H][W] (uint8 planes that already hold Y, Cb, Cr in full
+ * range, JFIF BT.601, as a2m_render_poses_u8 writes them from a converted palette) into the
+ * entropy-coded scans of baseline sequential JPEG files: SOF0, 8-bit, three components, 4:4:4
+ * (every sampling factor 1), one interleaved scan.  The scans are compacted back to back in `out`;
+ * offsets [N+1] (int64, DEVICE) receives each frame's first byte and, in offsets[N], the total.
+ * The header (SOI .. SOS) and EOI are the caller's (a2m/jpeg.py: jpeg_header); the scan depends on
+ * nothing in them but the tables below.  frames, out, offsets and ws are DEVICE pointers; qluma and
+ * qchroma are HOST pointers to 64 quantisers each in natural order (entry 8v + u divides
+ * coefficient (v, u)) and travel to the kernels by value.
+ *
+ * The byte stream (tests/jpeg_ref.py restates it; the device bytes equal it bit for bit).
+ *  Blocks.  MW = ceil(W/8), MH = ceil(H/8) MCUs of one 8x8 block per component, in the order
+ *   Y, Cb, Cr.  Pixel (8r + y, 8m + x) of block (r, m) is read at (min(., H-1), min(., W-1)): the
+ *   last row and column are replicated into the edge blocks.
+ *  Level shift and DCT, in 32-bit integers.  s[y][x] = pixel - 128.  M[u][x] =
+ *   round(2^13 * c(u)/2 * cos((2x+1) u pi/16)) with c(0) = 1/sqrt(2), c(u>0) = 1: M[0][x] =
+ *   A2M_JPEG_C0 and, for u > 0, M[u][x] = +-A2M_JPEG_Ck with k pi/16 the angle folded into the
+ *   first quadrant.  Rows first, t[y][u] = (sum_x s[y][x] M[u][x] + 2^6) >> 7 (six fraction bits
+ *   kept), then columns, d[v][u] = (sum_y t[y][u] M[v][y] + 2^18) >> 19.  >> is arithmetic: both
+ *   roundings are floor(z + 1/2).  Largest |sum|: 2.97e6, then 5.4e8.
+ *  Quantisation.  q = sign(d) * ((2 |d| + Q) / (2 Q)), the division truncating: |d| / Q rounded
+ *   half away from zero.  |q| is then limited to 1024 (DC) or 1023 (AC), which no input reaches
+ *   (|d| <= 1024 and <= 928) and which guarantees a code for every symbol.
+ *  Entropy coding.  Zig-zag order; DC as the difference to the previous block of the same
+ *   component; Huffman tables: the typical tables K.3-K.6 of ITU-T T.81 Annex K (luma tables for
+ *   Y, chroma tables for Cb and Cr), which code all 12 DC categories and all 162 AC symbols; value
+ *   bits as T.81 F.1.2; ZRL for runs of 16 zeros; EOB unless coefficient 63 is nonzero.
+ *  Restart intervals.  One MCU row is one interval (DRI = MW): the DC predictors start at 0 in
+ *   each, its last byte is filled with 1-bits, every 0xFF byte is followed by 0x00, and every
+ *   interval but a frame's last is followed by RSTn, n = r mod 8 for MCU row r.  A frame's scan
+ *   ends with its last interval's last byte (EOI is not written).
+ *
+ * Capacity.  `capacity` is the size of `out` in bytes.  offsets is always written in full; bytes
+ * at or past the capacity are dropped, never written.  offsets[N] > capacity therefore is the
+ * overflow flag and offsets[N] the size a second call needs (out may be NULL with capacity 0, to
+ * size alone).  ws: a2m_jpeg_ws_bytes(N, W, H) bytes (the quantised coefficients, the blocks' bit
+ * positions, A2M_JPEG_MAX_BLOCK_BYTES of scan scratch per block: 22 bits of DC and 63 x 26 bits of
+ * AC at most); the call allocates nothing, is six stream-ordered launches and can be captured in
+ * a HIP graph.  The only atomics OR disjoint bits into zeroed words, so the bytes are a pure
+ * function of the input.  A2M_EINVAL: a null pointer with N > 0; N < 0; W or H < 1 or > 65535; a
+ * quantiser of 0 or above 255 (baseline tables are 8-bit); capacity < 0; ws_bytes too small; more
+ * than INT32_MAX intervals (N ceil(H/8)) or 4 INT32_MAX blocks (one launch covers them).
+ * N = 0 returns A2M_OK without a launch and accepts NULL pointers. */
+#define A2M_JPEG_C0 2896 /* 2^12 / sqrt(2) */
+#define A2M_JPEG_C1 4017 /* 2^12 cos(1 pi/16) */
+#define A2M_JPEG_C2 3784
+#define A2M_JPEG_C3 3406
+#define A2M_JPEG_C4 2896
+#define A2M_JPEG_C5 2276
+#define A2M_JPEG_C6 1567
+#define A2M_JPEG_C7 799
+#define A2M_JPEG_PASS1_SHIFT 7
+#define A2M_JPEG_PASS2_SHIFT 19
+#define A2M_JPEG_MAX_BLOCK_BYTES 208
+size_t a2m_jpeg_ws_bytes(int32_t N, int32_t W, int32_t H); /* 0 for sizes the encoder refuses */
+int a2m_jpeg_encode_u8(const uint8_t* frames, int32_t N, int32_t W, int32_t H,
+                       const uint16_t* qluma, const uint16_t* qchroma, uint8_t* out,
+                       int64_t capacity, int64_t* offsets, void* ws, size_t ws_bytes, void* stream);
+
 /* Measurement hook (bench.py): while enabled, every launch of the implicit-GEMM engine (up to
  * 1024 per window; more make _read fail) carries a record of span stamps that its tile kernel and
  * split-K reduce write themselves (earliest block start, latest wave end on the GPU's constant-rate
