@@ -121,6 +121,11 @@ SIGNATURES = {
                                                P, P, I64, I64, I64, P, SZ, P]),
     'a2m_conv1d_wino_group_fwd_f32': (ctypes.c_int, [P, I64, I64, I64, I32, I32, I32, I32, P, I64, P, I32, P, P,
                                                      P, P, F32, I32, F32, P, P, I64, I64, I64, I64, P, SZ, P]),
+    'a2m_conv1d_down_pack_f32': (ctypes.c_int, [P, I32, I32, P, P]),
+    'a2m_conv1d_down_route': (ctypes.c_int, [P, I64, I64, I32, I32, I32, P, I32, I32, I32, I32, P, I64, I64, I64,
+                                             I32, ctypes.POINTER(I32)]),
+    'a2m_conv1d_down_fwd_f32': (ctypes.c_int, [P, I64, I64, I32, I32, I32, P, P, I32, I32, I32, I32, P, P, P, P,
+                                               F32, I32, F32, P, I64, I64, I64, P, SZ, P]),
     'a2m_dropout_f32': (ctypes.c_int, [P, I64, F32, U64, P, P]),
     'a2m_sum_bt_f32': (ctypes.c_int, [P, I64, I64, I64, I32, I32, I32, P, I32, P]),
     'a2m_layernorm_bwd_f32': (ctypes.c_int, [P, I64, I64, I64, I32, P, I32, I32, P, P, P, P, P, P, P, SZ, P]),

@@ -167,13 +167,77 @@ def conv1d_wino(x, w, b=None, bn=None, act=ACT_NONE, slope=0.2, out=None, cache=
     return out
 
 
+ROUTE_DOWN = 32   # flags bit of a2m_conv1d_down_route: the launch takes the Toom-Cook F(2,2) down-sampling tile
+
+
+def conv1d_down_packed(w, cache=None):
+    """Toom-Cook F(2,2) points of 4-tap stride-2 conv1d weights, [Co][Ci/32][6][32]
+    (a2m_conv1d_down_pack_f32), cached in `cache` per weight version under its own key."""
+    key = _wkey((w,)) + ('down',)
+    if cache is not None and cache.get('down_key') == key:
+        return cache['down_w']
+    Co, Ci, ks = w.shape
+    assert ks == 4
+    packed = torch.empty(Co * Ci * 6, device=w.device)
+    N.check(N.lib.a2m_conv1d_down_pack_f32(_p(w), Co, Ci, _p(packed), _stream()))
+    if cache is not None:
+        cache.update(down_key=key, down_w=packed)
+    return packed
+
+
+def conv1d_down_route(x, Co, out, down=True, ks=4, stride=2, pad=1):
+    """The engine's route for the conv1d of t-contiguous x [B, Ci, Tin] into out, with or without
+    the request for the down-sampling tile (a2m_conv1d_down_route; no launch): dict as
+    conv1d_wino_route's (flags & ROUTE_DOWN: that tile; otherwise the route of a2m_conv1d_fwd_f32).
+    None where x is not t-contiguous or the library has no such entry."""
+    B, Ci, Tin = x.shape
+    if not hasattr(N.lib, 'a2m_conv1d_down_route') or x.stride(2) != 1:
+        return None
+    Tout = out.shape[2]
+    xsb, ysb = (Tin, Tout * out.stride(2)) if B == 1 else (x.stride(0), out.stride(0))
+    o = (ctypes.c_int32 * 8)()
+    rc = N.lib.a2m_conv1d_down_route(_p(x), xsb, x.stride(1), B, Ci, Tin, _p(x), Co, ks, stride, pad, _p(out), ysb,
+                                     out.stride(1), out.stride(2), 1 if down else 0, o)
+    if rc != 0:
+        return None
+    return dict(zip(('kind', 'tile', 'bk', 'splits', 'kchunk', 'ma', 'mb', 'flags'), o))
+
+
+def _down_taken(x, Co, out):
+    r = conv1d_down_route(x, Co, out, True)
+    return r is not None and bool(r['flags'] & ROUTE_DOWN)
+
+
+def conv1d_down(x, w, b=None, bn=None, act=ACT_NONE, slope=0.2, out=None, cache=None):
+    """4-tap stride-2 pad-1 conv1d on the Toom-Cook F(2,2) tile (a2m_conv1d_down_fwd_f32: no im2col
+    matrix); raises where the engine refuses it (see conv1d(wino=True) for the request with a
+    fallback)."""
+    _check_dev(x, w, b, out)
+    B, Ci, Tin = x.shape
+    Co, Tout = w.shape[0], Tin // 2
+    assert w.shape[1:] == (Ci, 4) and w.is_contiguous() and x.stride(2) == 1
+    if out is None:
+        out = torch.empty(B, Co, Tout, device=x.device, dtype=x.dtype)
+    assert tuple(out.shape) == (B, Co, Tout)
+    xs, ys = list(x.stride()), list(out.stride())
+    if B == 1:
+        xs[0], ys[0] = Tin, Tout * ys[2]
+    packed = conv1d_down_packed(w, cache)
+    _with_ws(x.device, lambda wp, wn: N.lib.a2m_conv1d_down_fwd_f32(
+        _p(x), xs[0], xs[1], B, Ci, Tin, _p(packed), _p(b), Co, 4, 2, 1, *_bn_args(bn), act, slope, _p(out),
+        ys[0], ys[1], ys[2], wp, wn, _stream()))
+    return out
+
+
 def conv1d(x, w, b=None, stride=1, pad=0, bn=None, act=ACT_NONE, slope=0.2, out=None, cache=None, wino=False):
     """x: [B, Ci, Tin] (any strides), w: [Co, Ci, k] (or [Co, Ci] for a linear / 1x1).
     Returns / fills out [B, Co, Tout] (any strides).  With `cache` (a dict owned by the module),
     stride-1 same-padded convs over clips that tile the GEMM's 64 rows run on the tap-chunked
     path (a2m_conv1d_tap_fwd_f32: no im2col matrix; packed weights kept in `cache`).  wino=True
     (with `cache`) asks for the Winograd F(2,3) tile; where the engine refuses it (shape, bf16
-    precision, a per-shape rule) the call takes exactly the path of wino=False."""
+    precision, a per-shape rule) the call takes exactly the path of wino=False.  The same flag
+    asks for the Toom-Cook F(2,2) down-sampling tile when (k, stride, pad) == (4, 2, 1)
+    (a2m_conv1d_down_fwd_f32), with the same fallback."""
     _check_dev(x, w, b, out)
     B, Ci, Tin = x.shape
     Co, ks = w.shape[0], (w.shape[2] if w.dim() == 3 else 1)
@@ -187,6 +251,8 @@ def conv1d(x, w, b=None, stride=1, pad=0, bn=None, act=ACT_NONE, slope=0.2, out=
         xs[0], ys[0] = Tin * xs[2], Tout * ys[2]
     if wino and cache is not None and ks == 3 and stride == 1 and pad == 1 and _wino_taken(x, Co, out):
         return conv1d_wino(x, w, b, bn, act, slope, out, cache)
+    if wino and cache is not None and (ks, stride, pad) == (4, 2, 1) and _down_taken(x, Co, out):
+        return conv1d_down(x, w, b, bn, act, slope, out, cache)
     if cache is not None and _tap_eligible(x, ks, stride, pad, Ci) and \
             Ci % N.lib.a2m_conv1d_tap_chunk() == 0:
         packed, chunk = conv1d_tap_packed(w, cache)

@@ -25,7 +25,8 @@ from . import functional as F
 ACT = {'relu': F.ACT_RELU, 'lrelu': F.ACT_LRELU}
 # the eval forwards of the stride-1 3-tap 1-D convs (ConvNormRelu, so ResBlock and the UNet too; also
 # the grouped decoder launches) ask the engine for the Winograd F(2,3) tile; the engine's route
-# takes it per shape (csrc/gemm_route.cpp) or runs the direct tap tile.  Training never asks.
+# takes it per shape (csrc/gemm_route.cpp) or runs the direct tap tile.  The same request puts the
+# 4-tap stride-2 down-sampling convs on the Toom-Cook F(2,2) tile.  Training never asks.
 _WINO = os.environ.get('A2M_WINO', '1') != '0'
 
 

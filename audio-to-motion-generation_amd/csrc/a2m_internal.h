@@ -133,7 +133,7 @@ int gemm_k_tile();
 // wino: A holds the weights packed by a2m_conv1d_wino_pack_f32 and the launch must take the
 // Winograd F(2,3) tile (K = 3 Ci, the direct conv's; A2M_EINVAL where gemm_route refuses it)
 int gemm(const Gather& A, const Gather& B, const Epilogue& E, int M, int N, int K, int batch,
-         void* ws, size_t ws_bytes, hipStream_t stream, int force_split = 0, int wino = 0);
+         void* ws, size_t ws_bytes, hipStream_t stream, int force_split = 0, int wino = 0, int down = 0);
 size_t gemm_ws_bytes(int M, int N, int K, int batch);
 // Two independent tap-chunked (mode 5) problems of equal M and N -- the two output phases of a
 // stride-2 ConvTranspose1d -- as one launch, each at one split (gemm.hip).  Returns

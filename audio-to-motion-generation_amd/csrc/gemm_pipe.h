@@ -740,5 +740,9 @@ void launch_pipe_pair(const GemmArgs& a0, const GemmArgs& a1, int nt0, int nt1, 
 // gemm_f32_pipe_wino.hip: the Winograd F(2,3) tile of the halo layout's problem class (a.A: the
 // weights packed by a2m_conv1d_wino_pack_f32, a.K and the split bounds those of the direct conv)
 void launch_pipe_wino(const GemmArgs& a, int batch, hipStream_t st);
+// gemm_f32_pipe_down.hip: the Toom-Cook F(2,2) tile of the 4-tap stride-2 pad-1 conv1d (a.A: the
+// weights packed by a2m_conv1d_down_pack_f32, a.B: the conv's gather of x, Lw = the input clip
+// length, a.N the output columns, a.K = 4 Ci and the split bounds those of the direct conv)
+void launch_pipe_down(const GemmArgs& a, int batch, hipStream_t st);
 
 }  // namespace a2m

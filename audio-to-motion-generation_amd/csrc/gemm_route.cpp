@@ -336,11 +336,72 @@ bool wino_rule(int M, int N, int K, int batch) {
   return true;
 }
 
+// Shape classes of requested, eligible 4-tap stride-2 launches that stay on the im2col route
+// (im2col1d_kernel and the dense tile) because it measured faster there; blocks and K (= 4 Ci) as
+// in kWinoDirect.  The table is empty: both shapes of the bench step measured faster on the
+// down-sampling tile, alone and in the step's kernel trace (profiles/down_conv.txt).
+struct DownDirectRule {
+  int64_t min_blocks, max_blocks;
+  int min_k, max_k;
+};
+static const std::vector<DownDirectRule> kDownDirect = {};
+bool down_rule(int M, int N, int K, int batch) {
+  const int64_t blocks = cdiv(M, 64) * cdiv(N, 64) * (int64_t)batch;
+  for (const DownDirectRule& d : kDownDirect)
+    if (blocks >= d.min_blocks && blocks <= d.max_blocks && K >= d.min_k && K <= d.max_k) return false;
+  return true;
+}
+
+// the Toom-Cook F(2,2) down-sampling tile (gemm_f32_pipe_down.hip) takes: fp32, dense packed
+// weights of 6 Ci floats a row, B the plain gather of a 4-tap stride-2 pad-1 conv1d over
+// t-contiguous, 16-byte aligned x [B][Ci][Tin] with whole 32-channel chunks and clips of Tin >= 16
+// that tile the 128 input samples of a 64-column tile, every offset below 2^29 floats
+static bool down_operands(const Gather& A, const Gather& B, const Epilogue& E, int ma, int M, int N, int K) {
+  if (K <= 0 || K % 128 != 0) return false;
+  const int Ci = K / 4, Tin = B.Lw;
+  const bool conv = B.tapconv == 0 && B.nhwc == 0 && !B.kcontig && B.R1 == 1 && B.K1 == 1 && B.K2 == 4 &&
+                    B.ar2 == 2 && B.bk2 == 1 && B.cw == -1 && B.ch == 0 && B.sw == 1 && B.divh == 1 &&
+                    B.divw == 1 && B.Lh == 1 && Tin == 2 * B.R2;
+  const bool clips = Tin >= 16 && Tin % 4 == 0 && 128 % Tin == 0;
+  const bool aligned = reinterpret_cast<uintptr_t>(B.base) % 16 == 0 && B.sr0 % 4 == 0 && B.sk0 % 4 == 0 &&
+                       B.bstride % 4 == 0 && B.sr0 >= 0 && B.sk0 >= 0;
+  return conv && clips && aligned && ma == 0 && A.sr0 == 6 * Ci && E.interp_T <= 0 &&
+         pipe_below((int64_t)(M - 1) * A.sr0 + 6 * Ci) &&
+         pipe_below((int64_t)((N - 1) / B.R2) * B.sr0 + Tin + (int64_t)Ci * B.sk0);
+}
+
 GemmRoute gemm_route(const Gather& A, const Gather& B, const Epilogue& E, int M, int N, int K, int batch,
                      int force_split, const RouteConfig& cfg) {
   GemmRoute r{};
   const int ma = r.ma = operand_mode(A, K), mb = r.mb = operand_mode(B, K);
   const int prec = cfg.prec;
+  // the down-sampling tile, on request only: the plan (tile, splits, kchunk in whole 128-k chunks
+  // of 32 channels) is the planner's for the direct conv's M x N x 4 Ci on the pipelined 64x64
+  // tile.  Refused: the caller's operands are those of no other kernel (A is the packed U), so
+  // a2m_conv1d_down_* take a2m_conv1d_fwd_f32's route with its operands instead.
+  if (cfg.down && prec == 0 && cfg.pipe_override != 0 &&
+      down_operands(A, B, E, ma, M, N, K) && down_rule(M, N, K, batch)) {
+    // The planner's table is the direct tile's, which splits K to put two blocks on a CU.  This
+    // tile issues three quarters of the MFMAs, and a launch that already has a block for every CU
+    // measured as fast or faster at one split, without slabs or a reduce launch (512x2048x2048:
+    // 38.2 us against 40.9 at the planner's 2 splits; 1024x1024x4096: 67.4 against 71.7 at its 4
+    // and 66.3 at 2; profiles/down_conv.txt).  Smaller launches keep the planner's splits.
+    const bool fills = cdiv(M, 64) * cdiv(N, 64) * (int64_t)batch >= 256;
+    const int fs = force_split == 0 && cfg.override_split == 0 && fills ? 1 : force_split;
+    const Plan p = launch_plan(M, N, K, batch, true, prec, 4, false, fs, true, cfg);
+    if (p.bm == 64) {
+      r.tile = p.bm; r.bk = p.bk; r.splits = p.splits; r.kchunk = p.kchunk;
+      assert(p.kchunk > 0 && p.kchunk % 128 == 0);
+      r.reduce = p.splits > 1;
+      r.mcontig = E.som == 1 && M > 1;
+      r.vec4 = epi_vec4(E, N, r.mcontig, r.reduce);
+      r.ks = 1;
+      r.kind = A2M_GEMM_KIND_PIPE;
+      r.pipe_mb = mb; r.pipe_ma = 0; r.pipe_nt = 0;
+      r.down = true;
+      return r;
+    }
+  }
   const int kquant = mb == 5 ? B.tapconv : 1;
   const bool pipe_on = cfg.pipe_override >= 0 ? cfg.pipe_override != 0 : true;
   const PipeOperands po = pipe_operands(A, B, ma, mb, M, N, K);

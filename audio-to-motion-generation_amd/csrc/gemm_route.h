@@ -14,6 +14,7 @@ struct RouteConfig {
   int override_tile, override_split;   // a2m_gemm_plan_override (tuning)
   int halo_on;          // A2M_GEMM_HALO
   int wino;             // this launch asks for the Winograd F(2,3) tile (a2m_conv1d_wino_*; not process-wide)
+  int down;             // this launch asks for the Toom-Cook F(2,2) down-sampling tile (a2m_conv1d_down_*; not process-wide)
 };
 
 struct GemmRoute {
@@ -24,6 +25,7 @@ struct GemmRoute {
   int ks;                     // gemm_tile wave groups (1 or 2)
   bool halo, vec4, mcontig, reduce, interp;
   bool wino;                  // kind PIPE as gemm_pipe_kernel_wino: A is the Winograd-packed weights
+  bool down;                  // kind PIPE as gemm_pipe_kernel_down: A is the weights packed by a2m_conv1d_down_pack_f32
 };
 
 // Pure: no HIP call, no allocation, no mutable file-scope state (A2M_GEMM_PLAN_RULES is parsed
@@ -43,5 +45,7 @@ bool plan_rule_splits(int M, int N, int K);
 // whether the per-shape rule table keeps a requested, eligible launch on the Winograd tile (false:
 // the direct tile measured faster for the shape class)
 bool wino_rule(int M, int N, int K, int batch);
+// the same for the down-sampling tile (false: the im2col route measured faster)
+bool down_rule(int M, int N, int K, int batch);
 
 }  // namespace a2m

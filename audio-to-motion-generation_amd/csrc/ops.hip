@@ -416,6 +416,25 @@ __global__ void conv1d_wino_pack_kernel(const float* w, int Co, int Ci, float* o
   }
 }
 
+// 4-tap stride-2 Conv1d weights [Co][Ci][4] -> Toom-Cook F(2,2) points [Co][Ci/32][6][32] in the
+// order gemm_pipe_kernel_down's k-steps read them: (w0, w2 | w1, w3 | w0 + w2, w1 + w3) -- planes
+// 0 and 2 of the odd input phase, of the even phase, then plane 1 of either
+__global__ void conv1d_down_pack_kernel(const float* w, int Co, int Ci, float* out) {
+  const int64_t total = (int64_t)Co * Ci;
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < total;
+       i += (int64_t)gridDim.x * blockDim.x) {
+    const int ci = (int)(i % Ci), co = (int)(i / Ci);
+    const float w0 = w[4 * i], w1 = w[4 * i + 1], w2 = w[4 * i + 2], w3 = w[4 * i + 3];
+    float* const o = out + (((int64_t)co * (Ci / 32) + ci / 32) * 6) * 32 + ci % 32;
+    o[0] = w0;
+    o[32] = w2;
+    o[64] = w1;
+    o[96] = w3;
+    o[128] = w0 + w2;
+    o[160] = w1 + w3;
+  }
+}
+
 // [wq; wk; wv] -> wcat [C/4 + C][C], biases -> bcat (zeros where a bias pointer is NULL)
 __global__ void stack_qkv_kernel(const float* wq, const float* bq, const float* wk, const float* bk,
                                  const float* wv, const float* bv, int C, float* wcat, float* bcat) {
@@ -856,6 +875,110 @@ int a2m_conv1d_wino_fwd_f32(const float* x, int64_t xs_b, int64_t xs_c, int32_t 
                             int64_t ys_t, void* ws, size_t ws_bytes, void* stream) {
   return a2m_conv1d_wino_group_fwd_f32(x, 0, xs_b, xs_c, 1, B, Ci, T, packed, 0, bias, Co, bn_w, bn_b, bn_rm, bn_rv,
                                        bn_eps, act, slope, res, y, 0, ys_b, ys_c, ys_t, ws, ws_bytes, stream);
+}
+
+int a2m_conv1d_down_pack_f32(const float* w, int32_t Co, int32_t Ci, float* packed, void* stream) {
+  A2M_CHECK_ARG(w && packed && Co > 0 && Ci > 0 && Ci % 32 == 0, "conv1d_down_pack: bad args Co=%d Ci=%d (Ci %% 32)",
+                Co, Ci);
+  A2M_CHECK_ARG(fits32((int64_t)Co * Ci * 6), "conv1d_down_pack: too large");
+  hipLaunchKernelGGL(conv1d_down_pack_kernel, dim3((unsigned)std::min<int64_t>(cdiv((int64_t)Co * Ci, 256), 8192)),
+                     dim3(256), 0, as_stream(stream), w, Co, Ci, packed);
+  A2M_LAUNCH_CHECK();
+  return A2M_OK;
+}
+
+// the operands of a conv1d over t-contiguous x as the engine sees them: down = 1 A the weights
+// packed by a2m_conv1d_down_pack_f32 (6 Ci floats a row) and B the conv's plain gather of x; down
+// = 0 those of a2m_conv1d_fwd_f32 (`w` the plain weights; the im2col matrix stands in by its
+// alignment only: for route queries)
+struct DownProblem {
+  Gather A, B;
+  Epilogue E;
+  int N, K;
+};
+static int down_problem(DownProblem& p, const float* x, int64_t xs_b, int64_t xs_c, int32_t B, int32_t Ci,
+                        int32_t Tin, const float* w, int32_t down, const float* bias, int32_t Co, int32_t ks,
+                        int32_t stride, int32_t pad, const float* bn_w, const float* bn_b, const float* bn_rm,
+                        const float* bn_rv, float bn_eps, int32_t act, float slope, float* y, int64_t ys_b,
+                        int64_t ys_c, int64_t ys_t) {
+  A2M_CHECK_ARG(x && w && y, "conv1d_down: null pointer");
+  A2M_CHECK_ARG(B > 0 && Ci > 0 && Tin > 0 && Co > 0 && ks > 0 && stride > 0 && pad >= 0,
+                "conv1d_down: bad shape B=%d Ci=%d T=%d Co=%d k=%d s=%d p=%d", B, Ci, Tin, Co, ks, stride, pad);
+  const int Tout = (Tin + 2 * pad - ks) / stride + 1;
+  A2M_CHECK_ARG(Tout > 0, "conv1d_down: empty output");
+  A2M_CHECK_ARG(fits32(xs_b) && fits32(xs_c) && fits32(ys_b) && fits32(ys_c) && fits32(ys_t) &&
+                    fits32((int64_t)B * xs_b) && fits32((int64_t)B * ys_b) && fits32((int64_t)Co * Ci * 6),
+                "conv1d_down: tensor too large for 32-bit offsets");
+  const int64_t K = (int64_t)Ci * ks, N = (int64_t)B * Tout;
+  p.K = (int)K; p.N = (int)N;
+  p.A = dense_rk(w, down ? 6 * Ci : (int)K);
+  Gather Bg{};
+  if (!down && ks > 1 && ks <= 8 && stride <= 2 && Co >= 128 && K % 4 == 0 && N * K < (1LL << 31)) {
+    Bg = dense_rk(reinterpret_cast<const float*>(uintptr_t(256)), (int)K);   // the im2col matrix (workspace head)
+  } else if (!down && ks == 1 && pad == 0 && stride == 1 && xs_b == (int64_t)Tin) {
+    Bg = xs_c == 1 ? dense_rk(x, 1) : dense_kr(x, (int)xs_c);
+    if (xs_c != 1) Bg.sr0 = 1;
+  } else {
+    Bg.base = x; Bg.bstride = 0;
+    Bg.sr0 = (int)xs_b; Bg.R1 = 1; Bg.R2 = Tout; Bg.ar1 = 0; Bg.ar2 = stride;
+    Bg.sk0 = (int)xs_c; Bg.K1 = 1; Bg.K2 = ks; Bg.bk1 = 0; Bg.bk2 = 1;
+    Bg.ch = 0; Bg.cw = -pad; Bg.divh = Bg.divw = 1; Bg.Lh = 1; Bg.Lw = Tin;
+    Bg.sh = 0; Bg.sw = 1;
+    Bg.kcontig = (ks == 1 && xs_c == 1) ? 1 : 0;
+  }
+  p.B = Bg;
+  Epilogue E = epi_bn(y, bias, bn_w, bn_b, bn_rm, bn_rv, bn_eps, act, slope);
+  E.N1 = 1; E.N2 = Tout; E.so0 = (int)ys_b; E.so1 = 0; E.so2 = (int)ys_t; E.som = (int)ys_c;
+  p.E = E;
+  return A2M_OK;
+}
+
+int a2m_conv1d_down_route(const float* x, int64_t xs_b, int64_t xs_c, int32_t B, int32_t Ci, int32_t Tin,
+                          const float* w, int32_t Co, int32_t ks, int32_t stride, int32_t pad, float* y,
+                          int64_t ys_b, int64_t ys_c, int64_t ys_t, int32_t down, int32_t out[8]) {
+  A2M_CHECK_ARG(out != nullptr, "conv1d_down_route: null out");
+  RouteConfig cfg = route_config();
+  DownProblem p;
+  GemmRoute r{};
+  if (down) {
+    const int rc = down_problem(p, x, xs_b, xs_c, B, Ci, Tin, w, 1, nullptr, Co, ks, stride, pad, nullptr, nullptr,
+                                nullptr, nullptr, 1e-5f, 0, 0.2f, y, ys_b, ys_c, ys_t);
+    if (rc != A2M_OK) return rc;
+    cfg.down = 1;
+    r = gemm_route(p.A, p.B, p.E, Co, p.N, p.K, 1, 0, cfg);
+  }
+  if (!r.down) {   // no request, or refused: a2m_conv1d_fwd_f32's route with its operands
+    const int rc = down_problem(p, x, xs_b, xs_c, B, Ci, Tin, w, 0, nullptr, Co, ks, stride, pad, nullptr, nullptr,
+                                nullptr, nullptr, 1e-5f, 0, 0.2f, y, ys_b, ys_c, ys_t);
+    if (rc != A2M_OK) return rc;
+    cfg.down = 0;
+    r = gemm_route(p.A, p.B, p.E, Co, p.N, p.K, 1, 0, cfg);
+  }
+  const int32_t o[8] = {r.kind, r.tile, r.bk, r.splits, r.kchunk, r.ma, r.mb,
+                        (r.vec4 ? 1 : 0) | (r.mcontig ? 2 : 0) | (r.halo ? 4 : 0) | (r.reduce ? 8 : 0) |
+                            (r.wino ? 16 : 0) | (r.down ? 32 : 0)};
+  for (int i = 0; i < 8; ++i) out[i] = o[i];
+  return A2M_OK;
+}
+
+int a2m_conv1d_down_fwd_f32(const float* x, int64_t xs_b, int64_t xs_c, int32_t B, int32_t Ci, int32_t Tin,
+                            const float* packed, const float* bias, int32_t Co, int32_t ks, int32_t stride,
+                            int32_t pad, const float* bn_w, const float* bn_b, const float* bn_rm,
+                            const float* bn_rv, float bn_eps, int32_t act, float slope, float* y, int64_t ys_b,
+                            int64_t ys_c, int64_t ys_t, void* ws, size_t ws_bytes, void* stream) {
+  DownProblem p;
+  const int rc = down_problem(p, x, xs_b, xs_c, B, Ci, Tin, packed, 1, bias, Co, ks, stride, pad, bn_w, bn_b, bn_rm,
+                              bn_rv, bn_eps, act, slope, y, ys_b, ys_c, ys_t);
+  if (rc != A2M_OK) return rc;
+  RouteConfig cfg = route_config();
+  cfg.down = 1;
+  A2M_CHECK_ARG((reinterpret_cast<uintptr_t>(packed) % 16) == 0 &&
+                    gemm_route(p.A, p.B, p.E, Co, p.N, p.K, 1, 0, cfg).down,
+                "conv1d_down: not a down-sampling launch (fp32, k = 4, s = 2, p = 1, Tin >= 16 with 128 %% Tin == 0, "
+                "Ci %% 32 == 0, x rows 16-byte aligned, and a shape the rule table keeps on it): B=%d Ci=%d Co=%d "
+                "Tin=%d k=%d s=%d p=%d precision %d",
+                B, Ci, Co, Tin, ks, stride, pad, cfg.prec);
+  return gemm(p.A, p.B, p.E, Co, p.N, p.K, 1, ws, ws_bytes, as_stream(stream), 0, 0, 1);
 }
 
 int a2m_convt1d_pack_f32(const float* w, int32_t Ci, int32_t Co, int32_t ks, int32_t stride,

@@ -209,6 +209,28 @@ int a2m_conv1d_wino_group_fwd_f32(const float* x, int64_t xs_g, int64_t xs_b, in
                                   const float* bn_rm, const float* bn_rv, float bn_eps, int32_t act,
                                   float slope, const float* res, float* y, int64_t ys_g, int64_t ys_b,
                                   int64_t ys_c, int64_t ys_t, void* ws, size_t ws_bytes, void* stream);
+/* Toom-Cook F(2,2) form of the 4-tap, stride-2, pad-1 conv1d (opt-in; a2m_conv1d_fwd_f32 is
+ * unchanged): no im2col matrix, and two outputs of a clip from 6 multiplies per input channel
+ * instead of 8, fp32 only.  The conv is two 2-tap convs over the odd and the even input samples;
+ * weights [Co][Ci][4] are packed once per weight version by a2m_conv1d_down_pack_f32 as
+ * [Co][Ci/32][6][32] (Co*Ci*6 floats): w0, w2, w1, w3, w0+w2, w1+w3.
+ * Eligible: fp32 precision, k = 4, s = 2, p = 1, x t-contiguous with 16-byte aligned rows (xs_b
+ * and xs_c multiples of 4), clips of Tin >= 16 with 128 % Tin == 0, Ci % 32 == 0, and a shape the
+ * engine's per-shape rule table keeps on this tile.  The forward returns A2M_EINVAL
+ * ("conv1d_down: not a down-sampling launch ...") otherwise; a2m_conv1d_down_route answers
+ * beforehand without launching: out as a2m_gemm_f32_route's, flags bit 5 set where the launch
+ * takes this tile.  With down = 0, and for a refused request, it is the route
+ * a2m_conv1d_fwd_f32 takes for the same conv (`w` is inspected for alignment only).  Workspace:
+ * split-K slabs only.  Epilogue and output strides as a2m_conv1d_fwd_f32. */
+int a2m_conv1d_down_pack_f32(const float* w, int32_t Co, int32_t Ci, float* packed, void* stream);
+int a2m_conv1d_down_route(const float* x, int64_t xs_b, int64_t xs_c, int32_t B, int32_t Ci, int32_t Tin,
+                          const float* w, int32_t Co, int32_t ks, int32_t stride, int32_t pad, float* y,
+                          int64_t ys_b, int64_t ys_c, int64_t ys_t, int32_t down, int32_t out[8]);
+int a2m_conv1d_down_fwd_f32(const float* x, int64_t xs_b, int64_t xs_c, int32_t B, int32_t Ci, int32_t Tin,
+                            const float* packed, const float* bias, int32_t Co, int32_t ks, int32_t stride,
+                            int32_t pad, const float* bn_w, const float* bn_b, const float* bn_rm,
+                            const float* bn_rv, float bn_eps, int32_t act, float slope, float* y, int64_t ys_b,
+                            int64_t ys_c, int64_t ys_t, void* ws, size_t ws_bytes, void* stream);
 /* The same split in two: the per-phase weight packing (packed: Ci*Co*k floats) and the
  * forward on packed weights (callers cache the packing while the weights are unchanged). */
 int a2m_convt1d_pack_f32(const float* w, int32_t Ci, int32_t Co, int32_t ks, int32_t stride,
