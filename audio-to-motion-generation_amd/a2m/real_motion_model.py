@@ -27,7 +27,9 @@ class _GraphTopology(nn.Module):
         self.register_buffer('body_edge_index_template', S.edge_index(0, S.NUM_BODY))
         self.register_buffer('hand_edge_index_template', S.edge_index(10, S.NUM_HAND))
         for part, n in (('body', S.NUM_BODY), ('hand', S.NUM_HAND)):
-            ptr, idx = S.in_neighbour_csr(getattr(self, f'{part}_edge_index_template'), n)
+            # symmetric: the model trains on this CSR (the layer backward needs every reverse edge)
+            ptr, idx = S.in_neighbour_csr(getattr(self, f'{part}_edge_index_template'), n,
+                                          symmetric=True)
             self.register_buffer(f'_{part}_nbr_ptr', ptr, persistent=False)
             self.register_buffer(f'_{part}_nbr_idx', idx, persistent=False)
             # the fused eval stack's row order / degrees / gather slots, built once per skeleton

@@ -52,14 +52,27 @@ def edge_index(lo, n):
     return torch.tensor(edges, dtype=torch.long).t().contiguous()
 
 
-def in_neighbour_csr(ei, n):
+def in_neighbour_csr(ei, n, symmetric=False):
     """CSR over targets: for node i the sources of edges into i, in edge order (the order a
     PyG scatter visits them).  Raises ValueError for topologies beyond the graph kernels'
     limits (include/a2m.h): <= 128 nodes, in-degree <= 7 (8 with GAT's self loop), and
-    ptr + idx entries <= 256 (the block-local CSR the kernels stage in LDS)."""
+    ptr + idx entries <= 256 (the block-local CSR the kernels stage in LDS).
+
+    symmetric=True also requires every edge j->i to have its reverse i->j as many times as it
+    occurs itself: the layer backward gathers over in-neighbours where the adjoint sums over
+    out-neighbours, so it is right on such topologies only (the forward takes any)."""
     src, dst = ei[0].tolist(), ei[1].tolist()
     if n > 128:
         raise ValueError(f'graph of {n} nodes: the graph kernels support at most 128')
+    if symmetric:
+        count = {}
+        for e in zip(src, dst):
+            count[e] = count.get(e, 0) + 1
+        for (s, d), c in count.items():
+            if count.get((d, s), 0) != c:
+                raise ValueError(f'edge {s}->{d} occurs {c} time(s) but its reverse {d}->{s} '
+                                 f'{count.get((d, s), 0)}: the graph layer backward needs a '
+                                 f'symmetric topology')
     ptr, idx = [0], []
     for i in range(n):
         idx += [s for s, d in zip(src, dst) if d == i]

@@ -113,7 +113,8 @@ __global__ __launch_bounds__(256, GL_WG_PER_CU) void graph_layer_kernel(
   const int li = lane & 31, lh = lane >> 5;
 
   // ---- prologue: node tile, U, CSR (independent loads, one barrier)
-  const int ne = min(nbr_ptr[J], 2 * GMAXN - (J + 1));
+  // (a topology without an edge may pass no nbr_idx)
+  const int ne = nbr_idx ? min(nbr_ptr[J], 2 * GMAXN - (J + 1)) : 0;
   {  // node tile: all 8 float4 loads of this thread in flight before the LDS writes
     constexpr int NL = GMAXN * (GF / 4) / 256;
     float4 v[NL];
@@ -138,7 +139,7 @@ __global__ __launch_bounds__(256, GL_WG_PER_CU) void graph_layer_kernel(
     int d = 0;
     if (n < NB) {
       const int f0 = (n / J) * J, ln = n % J;
-      for (int e = csr[ln]; e < csr[ln + 1] && d < GMAXDEG; ++e) nbl[n][d++] = f0 + csr[J + 1 + e];
+      for (int e = csr[ln]; e < min(csr[ln + 1], ne) && d < GMAXDEG; ++e) nbl[n][d++] = f0 + csr[J + 1 + e];
       if (kind == 0 && d < GMAXDEG) nbl[n][d++] = n;
     }
     for (int q = d; q < GMAXDEG; ++q) nbl[n][q] = 0;
@@ -1172,7 +1173,8 @@ extern "C" int a2m_graph_layer_fwd_f32(const float* x, int32_t F, int32_t J, int
                                        float* lin_out, float* pre_ln, void* ws, size_t ws_bytes,
                                        void* stream) {
   (void)lin_out;
-  A2M_CHECK_ARG(x && y && nbr_ptr && nbr_idx && w0 && bias && (!norm_res || (ln_w && ln_b)),
+  // nbr_idx may be null for a topology without an edge (nbr_ptr[J] == 0; the kernel reads none then)
+  A2M_CHECK_ARG(x && y && nbr_ptr && w0 && bias && (!norm_res || (ln_w && ln_b)),
                 "graph_layer: null pointer");
   A2M_CHECK_ARG(J > 0 && J <= GMAXN && F >= 0, "graph_layer: bad J=%d", J);
   A2M_CHECK_ARG(kind == 0 ? (att_src && att_dst) : (kind == 1 && w1), "graph_layer: bad kind/params");

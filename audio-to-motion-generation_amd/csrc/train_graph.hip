@@ -141,7 +141,8 @@ __global__ __launch_bounds__(BNT) void graph_layer_bwd_kernel(
   const bool load_o = saved && norm_res;
   // ---- prologue: every global load of the block issued before the first LDS write (oldest
   // first: what the first barrier needs, then the weight fragments and dy rows that stay in flight)
-  const int ne = min(nbr_ptr[J], 2 * BMAXN - (J + 1));
+  // (a topology without an edge may pass no nbr_idx)
+  const int ne = nbr_idx ? min(nbr_ptr[J], 2 * BMAXN - (J + 1)) : 0;
   constexpr int NL = BMAXN * (BF / 4) / BNT;
   float4 v[NL], u[NL];
 #pragma unroll
@@ -187,7 +188,7 @@ __global__ __launch_bounds__(BNT) void graph_layer_bwd_kernel(
     int d = 0;
     if (n < NB) {
       const int f0 = (n / J) * J, ln = n % J;
-      for (int e = csr[ln]; e < csr[ln + 1] && d < BDEG; ++e) nbl[n][d++] = f0 + csr[J + 1 + e];
+      for (int e = csr[ln]; e < min(csr[ln + 1], ne) && d < BDEG; ++e) nbl[n][d++] = f0 + csr[J + 1 + e];
       if (kind == 0 && d < BDEG) nbl[n][d++] = n;
     }
     for (int q = d; q < BDEG; ++q) nbl[n][q] = 0;  // unpredicated gathers read row 0, weight 0
@@ -593,7 +594,8 @@ extern "C" int a2m_graph_layer_bwd_saved_f32(const float* x, const float* dy, co
                                              float* dw0, float* dw1, float* datt_src, float* datt_dst,
                                              float* dbias, float* dln_w, float* dln_b, void* ws, size_t ws_bytes,
                                              void* stream) {
-  A2M_CHECK_ARG(x && dy && dx && nbr_ptr && nbr_idx && w0 && bias && dw0 && dbias,
+  // nbr_idx may be null for a topology without an edge (nbr_ptr[J] == 0; the kernel reads none then)
+  A2M_CHECK_ARG(x && dy && dx && nbr_ptr && w0 && bias && dw0 && dbias,
                 "graph_layer_bwd: null pointer");
   A2M_CHECK_ARG(J > 0 && J <= BMAXN && F > 0, "graph_layer_bwd: bad shape");
   A2M_CHECK_ARG(kind == 0 ? (att_src && att_dst && datt_src && datt_dst) : (kind == 1 && w1 && dw1),

@@ -452,7 +452,8 @@ int a2m_to_bf16_f32(const float* x, void* y, int64_t n, void* stream);
  * The topology is given as an in-neighbour CSR over one graph (nbr_ptr[J+1], nbr_idx,
  * source nodes of the edges into each target, in edge order) and is shared by all F
  * frames (limits as for a2m_graph_stack_fwd_f32: J <= 128, in-degree <= 7,
- * (J + 1) + nbr_ptr[J] <= 256; not checked on the device arrays).  norm_res = 0 gives the bare layer y = L(x) (the discriminator's per-sample
+ * (J + 1) + nbr_ptr[J] <= 256; not checked on the device arrays).  A topology without an edge
+ * (nbr_ptr all zero) may pass nbr_idx = NULL, here and to the layer backward.  norm_res = 0 gives the bare layer y = L(x) (the discriminator's per-sample
  * GATConv, real_motion_model.py:602-616).  lin_out (GAT: x' [F*J][256]; GraphConv: aggregated x [F*J][64]) and
  * pre_ln [F*J][64] are saved for the backward pass when not NULL. */
 int a2m_graph_layer_fwd_f32(const float* x, int32_t F, int32_t J, int32_t kind,
@@ -598,7 +599,13 @@ int a2m_channel_attention_bwd_f32(const float* dy, const float* x, int32_t B, in
                                   const float* b2, float* dx, float* dw1, float* db1, float* dw2,
                                   float* db2, void* ws, size_t ws_bytes, void* stream);
 
-/* Skeleton graph layer backward (recomputes the forward from x). */
+/* Skeleton graph layer backward (recomputes the forward from x).
+   The topology must be symmetric: every edge j->i of the in-neighbour CSR has its reverse i->j,
+   as many times as it occurs itself.  The kernel gathers dx, the source-logit gradients and the
+   saved path's aggregation adjoint over a node's in-neighbours, where the adjoint sums over its
+   out-neighbours; on a directed topology these are wrong and no error is raised.  A directed
+   topology is valid for the forward entries only (a2m_graph_layer_fwd_f32, a2m_graph_stack_*).
+   skeleton.in_neighbour_csr(..., symmetric=True) checks the requirement. */
 int a2m_graph_layer_bwd_f32(const float* x, const float* dy, int32_t F, int32_t J, int32_t kind,
                             int32_t norm_res, const int32_t* nbr_ptr, const int32_t* nbr_idx,
                             const float* w0, const float* w1, const float* att_src,
@@ -608,7 +615,8 @@ int a2m_graph_layer_bwd_f32(const float* x, const float* dy, int32_t F, int32_t 
                             float* dln_b, void* ws, size_t ws_bytes, void* stream);
 /* The same with the forward's saved pre-LayerNorm output (a2m_graph_layer_fwd_f32's pre_ln,
    norm_res layers; NULL = recompute): no forward recompute in the backward kernel, and the
-   weight gradients contract the aggregation adjoint of dout with x (same sums, another order). */
+   weight gradients contract the aggregation adjoint of dout with x (same sums, another order).
+   The same symmetric-topology requirement as a2m_graph_layer_bwd_f32. */
 int a2m_graph_layer_bwd_saved_f32(const float* x, const float* dy, const float* pre_ln, int32_t F,
                                   int32_t J, int32_t kind, int32_t norm_res, const int32_t* nbr_ptr,
                                   const int32_t* nbr_idx, const float* w0, const float* w1,
