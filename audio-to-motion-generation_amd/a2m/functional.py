@@ -90,19 +90,42 @@ def _tap_eligible(x, ks, stride, pad, Ci):
             (x.stride(0) % 4 == 0 or x.shape[0] == 1) and x.stride(1) % 4 == 0)
 
 
+def _packed(cache, slot, w, tag, n, pack):
+    """The n packed floats that pack(ptr) writes for weight w, kept in cache[slot + 'w'] under
+    cache[slot + 'key'] = (weight version, *tag) and rebuilt when that key changes."""
+    key = _wkey((w,)) + tag
+    if cache is not None and cache.get(slot + 'key') == key:
+        return cache[slot + 'w']
+    packed = torch.empty(n, device=w.device)
+    N.check(pack(_p(packed)))
+    if cache is not None:
+        cache.update({slot + 'key': key, slot + 'w': packed})
+    return packed
+
+
+def _batch_strides(x, out):
+    """Batch strides of x / out [B, C, T] for the C entries: with one clip the batch stride is
+    irrelevant, so single-batch row views are made to look uniform."""
+    if x.shape[0] == 1:
+        return x.shape[2] * x.stride(2), out.shape[2] * out.stride(2)
+    return x.stride(0), out.stride(0)
+
+
+def _route(query):
+    """The dict of a route query (query(out) fills int32 out[8]); None where the query refuses."""
+    o = (ctypes.c_int32 * 8)()
+    if query(o) != 0:
+        return None
+    return dict(zip(('kind', 'tile', 'bk', 'splits', 'kchunk', 'ma', 'mb', 'flags'), o))
+
+
 def conv1d_tap_packed(w, cache=None):
     """Tap-chunked conv1d weights [Co][Ci/chunk][k][chunk] for the engine's current k-tile
     (a2m_conv1d_tap_pack_f32), cached in `cache` per weight version and chunk."""
     chunk = N.lib.a2m_conv1d_tap_chunk()
-    key = _wkey((w,)) + (chunk,)
-    if cache is not None and cache.get('key') == key:
-        return cache['w'], chunk
     Co, Ci, ks = w.shape
-    packed = torch.empty(Co * Ci * ks, device=w.device)
-    N.check(N.lib.a2m_conv1d_tap_pack_f32(_p(w), Co, Ci, ks, chunk, _p(packed), _stream()))
-    if cache is not None:
-        cache.update(key=key, w=packed)
-    return packed, chunk
+    return _packed(cache, '', w, (chunk,), Co * Ci * ks, lambda o: N.lib.a2m_conv1d_tap_pack_f32(
+        _p(w), Co, Ci, ks, chunk, o, _stream())), chunk
 
 
 ROUTE_WINO = 16   # flags bit of a2m_conv1d_wino_route: the launch takes the Winograd F(2,3) tile
@@ -111,16 +134,10 @@ ROUTE_WINO = 16   # flags bit of a2m_conv1d_wino_route: the launch takes the Win
 def conv1d_wino_packed(w, cache=None):
     """Winograd F(2,3) points of 3-tap conv1d weights, [Co][Ci/32][4][32]
     (a2m_conv1d_wino_pack_f32), cached in `cache` per weight version under its own key."""
-    key = _wkey((w,)) + ('wino',)
-    if cache is not None and cache.get('wino_key') == key:
-        return cache['wino_w']
     Co, Ci, ks = w.shape
     assert ks == 3
-    packed = torch.empty(Co * Ci * 4, device=w.device)
-    N.check(N.lib.a2m_conv1d_wino_pack_f32(_p(w), Co, Ci, _p(packed), _stream()))
-    if cache is not None:
-        cache.update(wino_key=key, wino_w=packed)
-    return packed
+    return _packed(cache, 'wino_', w, ('wino',), Co * Ci * 4, lambda o: N.lib.a2m_conv1d_wino_pack_f32(
+        _p(w), Co, Ci, o, _stream()))
 
 
 def conv1d_wino_route(x, Co, out, wino=True, G=1, xs_g=0, ys_g=0):
@@ -131,13 +148,10 @@ def conv1d_wino_route(x, Co, out, wino=True, G=1, xs_g=0, ys_g=0):
     B, Ci, T = x.shape
     if not hasattr(N.lib, 'a2m_conv1d_wino_route') or not _tap_eligible(x, 3, 1, 1, Ci):
         return None
-    xsb, ysb = (T * x.stride(2), T * out.stride(2)) if B == 1 else (x.stride(0), out.stride(0))
-    o = (ctypes.c_int32 * 8)()
-    rc = N.lib.a2m_conv1d_wino_route(_p(x), xs_g, xsb, x.stride(1), G, B, Ci, T, _p(x), Co, None, _p(out), ys_g,
-                                     ysb, out.stride(1), out.stride(2), 1 if wino else 0, o)
-    if rc != 0:
-        return None
-    return dict(zip(('kind', 'tile', 'bk', 'splits', 'kchunk', 'ma', 'mb', 'flags'), o))
+    xsb, ysb = _batch_strides(x, out)
+    return _route(lambda o: N.lib.a2m_conv1d_wino_route(
+        _p(x), xs_g, xsb, x.stride(1), G, B, Ci, T, _p(x), Co, None, _p(out), ys_g, ysb, out.stride(1),
+        out.stride(2), 1 if wino else 0, o))
 
 
 def _wino_taken(x, Co, out, **kw):
@@ -157,13 +171,11 @@ def conv1d_wino(x, w, b=None, bn=None, act=ACT_NONE, slope=0.2, out=None, cache=
         out = torch.empty(B, Co, T, device=x.device, dtype=x.dtype)
     assert tuple(out.shape) == (B, Co, T)
     assert res is None or (res.shape == out.shape and res.stride() == out.stride())
-    xs, ys = list(x.stride()), list(out.stride())
-    if B == 1:
-        xs[0], ys[0] = T * xs[2], T * ys[2]
+    xsb, ysb = _batch_strides(x, out)
     packed = conv1d_wino_packed(w, cache)
     _with_ws(x.device, lambda wp, wn: N.lib.a2m_conv1d_wino_fwd_f32(
-        _p(x), xs[0], xs[1], B, Ci, T, _p(packed), _p(b), Co, *_bn_args(bn), act, slope, _p(res), _p(out),
-        ys[0], ys[1], ys[2], wp, wn, _stream()))
+        _p(x), xsb, x.stride(1), B, Ci, T, _p(packed), _p(b), Co, *_bn_args(bn), act, slope, _p(res), _p(out),
+        ysb, out.stride(1), out.stride(2), wp, wn, _stream()))
     return out
 
 
@@ -173,16 +185,10 @@ ROUTE_DOWN = 32   # flags bit of a2m_conv1d_down_route: the launch takes the Too
 def conv1d_down_packed(w, cache=None):
     """Toom-Cook F(2,2) points of 4-tap stride-2 conv1d weights, [Co][Ci/32][6][32]
     (a2m_conv1d_down_pack_f32), cached in `cache` per weight version under its own key."""
-    key = _wkey((w,)) + ('down',)
-    if cache is not None and cache.get('down_key') == key:
-        return cache['down_w']
     Co, Ci, ks = w.shape
     assert ks == 4
-    packed = torch.empty(Co * Ci * 6, device=w.device)
-    N.check(N.lib.a2m_conv1d_down_pack_f32(_p(w), Co, Ci, _p(packed), _stream()))
-    if cache is not None:
-        cache.update(down_key=key, down_w=packed)
-    return packed
+    return _packed(cache, 'down_', w, ('down',), Co * Ci * 6, lambda o: N.lib.a2m_conv1d_down_pack_f32(
+        _p(w), Co, Ci, o, _stream()))
 
 
 def conv1d_down_route(x, Co, out, down=True, ks=4, stride=2, pad=1):
@@ -193,14 +199,10 @@ def conv1d_down_route(x, Co, out, down=True, ks=4, stride=2, pad=1):
     B, Ci, Tin = x.shape
     if not hasattr(N.lib, 'a2m_conv1d_down_route') or x.stride(2) != 1:
         return None
-    Tout = out.shape[2]
-    xsb, ysb = (Tin, Tout * out.stride(2)) if B == 1 else (x.stride(0), out.stride(0))
-    o = (ctypes.c_int32 * 8)()
-    rc = N.lib.a2m_conv1d_down_route(_p(x), xsb, x.stride(1), B, Ci, Tin, _p(x), Co, ks, stride, pad, _p(out), ysb,
-                                     out.stride(1), out.stride(2), 1 if down else 0, o)
-    if rc != 0:
-        return None
-    return dict(zip(('kind', 'tile', 'bk', 'splits', 'kchunk', 'ma', 'mb', 'flags'), o))
+    xsb, ysb = _batch_strides(x, out)
+    return _route(lambda o: N.lib.a2m_conv1d_down_route(
+        _p(x), xsb, x.stride(1), B, Ci, Tin, _p(x), Co, ks, stride, pad, _p(out), ysb, out.stride(1), out.stride(2),
+        1 if down else 0, o))
 
 
 def _down_taken(x, Co, out):
@@ -219,13 +221,11 @@ def conv1d_down(x, w, b=None, bn=None, act=ACT_NONE, slope=0.2, out=None, cache=
     if out is None:
         out = torch.empty(B, Co, Tout, device=x.device, dtype=x.dtype)
     assert tuple(out.shape) == (B, Co, Tout)
-    xs, ys = list(x.stride()), list(out.stride())
-    if B == 1:
-        xs[0], ys[0] = Tin, Tout * ys[2]
+    xsb, ysb = _batch_strides(x, out)
     packed = conv1d_down_packed(w, cache)
     _with_ws(x.device, lambda wp, wn: N.lib.a2m_conv1d_down_fwd_f32(
-        _p(x), xs[0], xs[1], B, Ci, Tin, _p(packed), _p(b), Co, 4, 2, 1, *_bn_args(bn), act, slope, _p(out),
-        ys[0], ys[1], ys[2], wp, wn, _stream()))
+        _p(x), xsb, x.stride(1), B, Ci, Tin, _p(packed), _p(b), Co, 4, 2, 1, *_bn_args(bn), act, slope, _p(out),
+        ysb, out.stride(1), out.stride(2), wp, wn, _stream()))
     return out
 
 
@@ -246,9 +246,7 @@ def conv1d(x, w, b=None, stride=1, pad=0, bn=None, act=ACT_NONE, slope=0.2, out=
     if out is None:
         out = torch.empty(B, Co, Tout, device=x.device, dtype=x.dtype)
     assert tuple(out.shape) == (B, Co, Tout), (out.shape, (B, Co, Tout))
-    xs, ys = list(x.stride()), list(out.stride())
-    if B == 1:  # batch stride is irrelevant; make single-batch row views look uniform
-        xs[0], ys[0] = Tin * xs[2], Tout * ys[2]
+    xsb, ysb = _batch_strides(x, out)
     if wino and cache is not None and ks == 3 and stride == 1 and pad == 1 and _wino_taken(x, Co, out):
         return conv1d_wino(x, w, b, bn, act, slope, out, cache)
     if wino and cache is not None and (ks, stride, pad) == (4, 2, 1) and _down_taken(x, Co, out):
@@ -257,12 +255,12 @@ def conv1d(x, w, b=None, stride=1, pad=0, bn=None, act=ACT_NONE, slope=0.2, out=
             Ci % N.lib.a2m_conv1d_tap_chunk() == 0:
         packed, chunk = conv1d_tap_packed(w, cache)
         _with_ws(x.device, lambda wp, wn: N.lib.a2m_conv1d_tap_fwd_f32(
-            _p(x), xs[0], xs[1], B, Ci, Tin, _p(packed), chunk, _p(b), Co, ks, pad,
-            *_bn_args(bn), act, slope, _p(out), ys[0], ys[1], ys[2], wp, wn, _stream()))
+            _p(x), xsb, x.stride(1), B, Ci, Tin, _p(packed), chunk, _p(b), Co, ks, pad,
+            *_bn_args(bn), act, slope, _p(out), ysb, out.stride(1), out.stride(2), wp, wn, _stream()))
         return out
     _with_ws(x.device, lambda wp, wn: N.lib.a2m_conv1d_fwd_f32(
-        _p(x), xs[0], xs[1], xs[2], B, Ci, Tin, _p(w), _p(b), Co, ks, stride, pad,
-        *_bn_args(bn), act, slope, _p(out), ys[0], ys[1], ys[2], wp, wn, _stream()))
+        _p(x), xsb, x.stride(1), x.stride(2), B, Ci, Tin, _p(w), _p(b), Co, ks, stride, pad,
+        *_bn_args(bn), act, slope, _p(out), ysb, out.stride(1), out.stride(2), wp, wn, _stream()))
     return out
 
 
@@ -278,26 +276,30 @@ def _group_stride(ts):
     return d // 4
 
 
-def conv1d_tap_group(xs, packed, chunk, bias, Co, ks, pad, bn, act, slope, outs):
-    """G same-shape tap-chunked conv1d problems in one launch (a2m_conv1d_tap_group_fwd_f32).
-    xs / outs: lists of G [B, Ci, T] / [B, Co, T] views with equal strides; packed [G, n] and
-    bias / BN tensors [G, Co] stacked per problem (see group_params)."""
+def _conv1d_group(entry, xs, packed, mid, Co, outs):
+    """One grouped launch of a C entry that takes (x, group / batch / channel strides, G, B, Ci, T,
+    packed, its group stride, *mid, y, its strides, workspace, stream)."""
     x0, y0 = xs[0], outs[0]
     _check_dev(x0, y0, packed)
     B, Ci, T = x0.shape
     assert all(x.stride() == x0.stride() and x.shape == x0.shape for x in xs)
     assert all(y.stride() == y0.stride() and tuple(y.shape) == (B, Co, T) for y in outs)
-    assert _tap_eligible(x0, ks, 1, pad, Ci) and Ci % chunk == 0 and chunk == N.lib.a2m_conv1d_tap_chunk()
-    G = len(xs)
     xs_g, ys_g = _group_stride(xs), _group_stride(outs)
-    xsb, ysb = x0.stride(0), y0.stride(0)
-    if B == 1:
-        xsb, ysb = T * x0.stride(2), T * y0.stride(2)
-    _with_ws(x0.device, lambda wp, wn: N.lib.a2m_conv1d_tap_group_fwd_f32(
-        _p(x0), xs_g, xsb, x0.stride(1), G, B, Ci, T, _p(packed), packed.stride(0), chunk, _p(bias), Co,
-        ks, pad, *_bn_args(bn), act, slope, _p(y0), ys_g, ysb, y0.stride(1), y0.stride(2), wp, wn,
-        _stream()))
+    xsb, ysb = _batch_strides(x0, y0)
+    _with_ws(x0.device, lambda wp, wn: entry(
+        _p(x0), xs_g, xsb, x0.stride(1), len(xs), B, Ci, T, _p(packed), packed.stride(0), *mid, _p(y0), ys_g, ysb,
+        y0.stride(1), y0.stride(2), wp, wn, _stream()))
     return outs
+
+
+def conv1d_tap_group(xs, packed, chunk, bias, Co, ks, pad, bn, act, slope, outs):
+    """G same-shape tap-chunked conv1d problems in one launch (a2m_conv1d_tap_group_fwd_f32).
+    xs / outs: lists of G [B, Ci, T] / [B, Co, T] views with equal strides; packed [G, n] and
+    bias / BN tensors [G, Co] stacked per problem (see group_params)."""
+    Ci = xs[0].shape[1]
+    assert _tap_eligible(xs[0], ks, 1, pad, Ci) and Ci % chunk == 0 and chunk == N.lib.a2m_conv1d_tap_chunk()
+    return _conv1d_group(N.lib.a2m_conv1d_tap_group_fwd_f32, xs, packed,
+                         [chunk, _p(bias), Co, ks, pad, *_bn_args(bn), act, slope], Co, outs)
 
 
 def conv1d_wino_group_taken(xs, Co, outs):
@@ -308,20 +310,8 @@ def conv1d_wino_group_taken(xs, Co, outs):
 def conv1d_wino_group(xs, packed, bias, Co, bn, act, slope, outs):
     """conv1d_tap_group on the Winograd F(2,3) tile (a2m_conv1d_wino_group_fwd_f32): packed [G, n]
     stacks each problem's conv1d_wino_packed weights."""
-    x0, y0 = xs[0], outs[0]
-    _check_dev(x0, y0, packed)
-    B, Ci, T = x0.shape
-    assert all(x.stride() == x0.stride() and x.shape == x0.shape for x in xs)
-    assert all(y.stride() == y0.stride() and tuple(y.shape) == (B, Co, T) for y in outs)
-    G = len(xs)
-    xs_g, ys_g = _group_stride(xs), _group_stride(outs)
-    xsb, ysb = x0.stride(0), y0.stride(0)
-    if B == 1:
-        xsb, ysb = T * x0.stride(2), T * y0.stride(2)
-    _with_ws(x0.device, lambda wp, wn: N.lib.a2m_conv1d_wino_group_fwd_f32(
-        _p(x0), xs_g, xsb, x0.stride(1), G, B, Ci, T, _p(packed), packed.stride(0), _p(bias), Co,
-        *_bn_args(bn), act, slope, None, _p(y0), ys_g, ysb, y0.stride(1), y0.stride(2), wp, wn, _stream()))
-    return outs
+    return _conv1d_group(N.lib.a2m_conv1d_wino_group_fwd_f32, xs, packed,
+                         [_p(bias), Co, *_bn_args(bn), act, slope, None], Co, outs)
 
 
 def linear(x, w, b=None, out=None):
@@ -337,30 +327,18 @@ def linear(x, w, b=None, out=None):
 
 def convt_packed(w, stride, pad, cache=None):
     """Phase-packed ConvTranspose1d weights (a2m_convt1d_pack_f32), cached in `cache`."""
-    key = _wkey((w,)) + (stride, pad)
-    if cache is not None and cache.get('key') == key:
-        return cache['w']
     Ci, Co, ks = w.shape
-    packed = torch.empty(Ci * Co * ks, device=w.device)
-    N.check(N.lib.a2m_convt1d_pack_f32(_p(w), Ci, Co, ks, stride, pad, _p(packed), _stream()))
-    if cache is not None:
-        cache.update(key=key, w=packed)
-    return packed
+    return _packed(cache, '', w, (stride, pad), Ci * Co * ks, lambda o: N.lib.a2m_convt1d_pack_f32(
+        _p(w), Ci, Co, ks, stride, pad, o, _stream()))
 
 
 def convt_tap_packed(w, stride, pad, cache=None):
     """Per-phase tap-chunked ConvTranspose1d weights for the engine's current k-tile
     (a2m_convt1d_tap_pack_f32), cached in `cache` per weight version and chunk."""
     chunk = N.lib.a2m_conv1d_tap_chunk()
-    key = _wkey((w,)) + (stride, pad, 'tap', chunk)
-    if cache is not None and cache.get('key') == key:
-        return cache['w'], chunk
     Ci, Co, ks = w.shape
-    packed = torch.empty(Ci * Co * ks, device=w.device)
-    N.check(N.lib.a2m_convt1d_tap_pack_f32(_p(w), Ci, Co, ks, stride, pad, chunk, _p(packed), _stream()))
-    if cache is not None:
-        cache.update(key=key, w=packed)
-    return packed, chunk
+    return _packed(cache, '', w, (stride, pad, 'tap', chunk), Ci * Co * ks, lambda o: N.lib.a2m_convt1d_tap_pack_f32(
+        _p(w), Ci, Co, ks, stride, pad, chunk, o, _stream())), chunk
 
 
 def _convt_tap_eligible(x, stride, Tout):
@@ -416,15 +394,9 @@ def conv2d(x, w, b=None, stride=1, pad=(0, 0), bn=None, act=ACT_NONE, slope=0.2,
 
 def conv2d_nhwc_packed(w, cache=None):
     """[Co][kh][kw][Ci] conv2d weights (a2m_conv2d_pack_nhwc_f32), cached per weight version."""
-    key = _wkey((w,))
-    if cache is not None and cache.get('key') == key:
-        return cache['w']
     Co, Ci, kh, kw = w.shape
-    packed = torch.empty(Co * kh * kw * Ci, device=w.device)
-    N.check(N.lib.a2m_conv2d_pack_nhwc_f32(_p(w), Co, Ci, kh, kw, _p(packed), _stream()))
-    if cache is not None:
-        cache.update(key=key, w=packed)
-    return packed
+    return _packed(cache, '', w, (), Co * kh * kw * Ci, lambda o: N.lib.a2m_conv2d_pack_nhwc_f32(
+        _p(w), Co, Ci, kh, kw, o, _stream()))
 
 
 def conv2d_nhwc(x, w, b=None, stride=1, pad=(0, 0), bn=None, act=ACT_NONE, slope=0.2, cols=None,

@@ -130,10 +130,16 @@ inline Epilogue epi_dense(float* out, int ldn, int64_t bstride = 0) {  // out[m]
 // independent problems (grid z), with optional split-K through workspace `ws`.
 // k-tile depth of the engine at the current precision (the chunk of tap-chunked conv weights)
 int gemm_k_tile();
-// wino: A holds the weights packed by a2m_conv1d_wino_pack_f32 and the launch must take the
-// Winograd F(2,3) tile (K = 3 Ci, the direct conv's; A2M_EINVAL where gemm_route refuses it)
+// The transform tile a launch asks for and a route names (gemm_pipe_xform.h): A then holds the
+// weights packed for that tile, which no other kernel can take
+enum Xform {
+  XFORM_NONE = 0,
+  XFORM_WINO = 1,   // Winograd F(2,3), 3-tap stride-1 pad-1 conv1d: a2m_conv1d_wino_pack_f32, K = 3 Ci (the direct conv's)
+  XFORM_DOWN = 2,   // Toom-Cook F(2,2), 4-tap stride-2 pad-1 conv1d: a2m_conv1d_down_pack_f32, K = 4 Ci
+};
+// xform: the launch must take that tile (A2M_EINVAL where gemm_route refuses it)
 int gemm(const Gather& A, const Gather& B, const Epilogue& E, int M, int N, int K, int batch,
-         void* ws, size_t ws_bytes, hipStream_t stream, int force_split = 0, int wino = 0, int down = 0);
+         void* ws, size_t ws_bytes, hipStream_t stream, int force_split = 0, Xform xform = XFORM_NONE);
 size_t gemm_ws_bytes(int M, int N, int K, int batch);
 // Two independent tap-chunked (mode 5) problems of equal M and N -- the two output phases of a
 // stride-2 ConvTranspose1d -- as one launch, each at one split (gemm.hip).  Returns

@@ -269,7 +269,7 @@ static int g_pair_override = -1;   // a2m_convt_pair_override: -1 default (gemm_
 RouteConfig route_config() {
   // A2M_GEMM_HALO=0: mode 5 re-stores the window shifted for every tap (the round-3 loader)
   static const int halo_on = env_int("A2M_GEMM_HALO", 1);
-  return {g_gemm_prec, g_pipe_override, g_pair_override, g_override_tile, g_override_split, halo_on, 0, 0};
+  return {g_gemm_prec, g_pipe_override, g_pair_override, g_override_tile, g_override_split, halo_on, XFORM_NONE};
 }
 
 int gemm_k_tile() { return gemm_bk(g_gemm_prec); }
@@ -294,12 +294,9 @@ static void fill_args(GemmArgs& a, const Gather& A, const Gather& B, const Epilo
 
 // the tile kernel the route names; false: the library carries no such kernel
 static bool launch_route(const GemmArgs& a, const GemmRoute& r, int prec, int batch, hipStream_t stream) {
-  if (r.kind == A2M_GEMM_KIND_PIPE && r.wino) {
-    launch_pipe_wino(a, batch, stream);
-    return true;
-  }
-  if (r.kind == A2M_GEMM_KIND_PIPE && r.down) {
-    launch_pipe_down(a, batch, stream);
+  if (r.kind == A2M_GEMM_KIND_PIPE && r.xform != XFORM_NONE) {
+    if (r.xform == XFORM_WINO) launch_pipe_wino(a, batch, stream);
+    else launch_pipe_down(a, batch, stream);
     return true;
   }
   if (r.kind == A2M_GEMM_KIND_PIPE)
@@ -323,20 +320,24 @@ static bool launch_route(const GemmArgs& a, const GemmRoute& r, int prec, int ba
   return true;
 }
 
+// per Xform: the tile's name in a refusal, its A2M_GEMM_LOG suffix and its timing-description suffix
+static const char* const kXformTile[] = {"", "Winograd", "down-sampling"};
+static const char* const kXformLog[] = {" (pipe)", " (pipe) (wino)", " (pipe) (down)"};
+static const char* const kXformDesc[] = {"", " wino", " down"};
+
 int gemm(const Gather& A, const Gather& B, const Epilogue& E, int M, int N, int K, int batch,
-         void* ws, size_t ws_bytes, hipStream_t stream, int force_split, int wino, int down) {
+         void* ws, size_t ws_bytes, hipStream_t stream, int force_split, Xform xform) {
   A2M_CHECK_ARG(M > 0 && N > 0 && K >= 0 && batch > 0, "gemm: bad sizes M=%d N=%d K=%d batch=%d",
                 M, N, K, batch);
   A2M_CHECK_ARG(E.interp_T <= 0 || (batch == 1 && E.interp_H > 0 && N % E.interp_H == 0 &&
                                     (size_t)E.interp_H * sizeof(float) <= 32768),
                 "gemm: fused resample needs batch 1, N a multiple of H = %d <= 8192", E.interp_H);
   RouteConfig cfg = route_config();
-  cfg.wino = wino;
-  cfg.down = down;
+  cfg.xform = xform;
   const GemmRoute r = gemm_route(A, B, E, M, N, K, batch, force_split, cfg);
-  // A holds Winograd-packed weights: no other kernel can take them
-  A2M_CHECK_ARG(!wino || r.wino, "gemm: the route refuses the Winograd tile for M=%d N=%d K=%d batch=%d", M, N, K, batch);
-  A2M_CHECK_ARG(!down || r.down, "gemm: the route refuses the down-sampling tile for M=%d N=%d K=%d batch=%d", M, N, K, batch);
+  // A holds the tile's packed weights: no other kernel can take them (a route names a tile on request only)
+  A2M_CHECK_ARG(r.xform == xform, "gemm: the route refuses the %s tile for M=%d N=%d K=%d batch=%d", kXformTile[xform], M,
+                N, K, batch);
   GemmArgs a;
   fill_args(a, A, B, E, M, N, K, r);
   if (r.reduce) {
@@ -350,12 +351,12 @@ int gemm(const Gather& A, const Gather& B, const Epilogue& E, int M, int N, int 
   static const int log_launches = env_int("A2M_GEMM_LOG", 0);
   if (log_launches)
     std::fprintf(stderr, "a2m gemm M=%d N=%d K=%d batch=%d tile=%d bk=%d splits=%d%s modes=%d,%d som=%d so=%d,%d,%d N12=%d,%d\n",
-                 M, N, K, batch, r.tile, r.bk, r.splits, r.wino ? " (pipe) (wino)" : r.down ? " (pipe) (down)" : r.kind == A2M_GEMM_KIND_PIPE ? " (pipe)" : "", r.ma, r.mb, E.som,
+                 M, N, K, batch, r.tile, r.bk, r.splits, r.kind == A2M_GEMM_KIND_PIPE ? kXformLog[r.xform] : "", r.ma, r.mb, E.som,
                  E.so0, E.so1, E.so2, E.N1, E.N2);
   if (timing_enabled()) {
     char desc[96];
     std::snprintf(desc, sizeof(desc), "M=%d N=%d K=%d b=%d tile=%d split=%d modes=%d,%d%s", M, N, K,
-                  batch, r.tile, r.splits, r.ma, r.mb, r.wino ? " wino" : r.down ? " down" : "");
+                  batch, r.tile, r.splits, r.ma, r.mb, kXformDesc[r.xform]);
     a.ts = timing_open(2.0 * M * N * (double)K * batch, desc, r.reduce, stream);
   }
   if (!launch_route(a, r, cfg.prec, batch, stream)) {

@@ -16,10 +16,10 @@
 //   step 2: wn = 0 (plane 1, odd)  -> acc1      wn = 1 (plane 1, even) -> acc1
 // 48 MFMAs a wave and chunk (64 in the direct tile), two accumulators.
 //   A: the packed U, [Co][Ci / 32][6][32] in the order (step, wn) above, read as dense rows of
-//      6 Ci (DownRows); a step's tile is its two units' 64 x 32 (stages by k-step parity).
+//      6 Ci (XformRows); a step's tile is its two units' 64 x 32 (stages by k-step parity).
 //   B: a thread loads 8 consecutive t (two pairs) of channels kq and kq + 16 plus x[t0 - 1] and
 //      x[t0 + 8], transforms them in registers and stores V[unit][pair][36] (pair rows permuted
-//      as in the Winograd tile).  The plane-0 / plane-2 units are single-buffered: the next
+//      by xform_pair_row).  The plane-0 / plane-2 units are single-buffered: the next
 //      chunk's are stored during step 2, which reads plane 1 only; the plane-1 units are stored
 //      with them into the stage of the other chunk parity.  The x window of chunk c + 1 is loaded
 //      at step 2 of chunk c - 1 and stored at step 2 of chunk c.
@@ -28,51 +28,14 @@
 // unchanged (vec4 / scalar / split-K slab: the transform is linear, so slabs hold outputs and
 // splitk_reduce_kernel serves).
 // LDS: 2 x 18 KB A stages + 8 x 4.5 KB V units = 72 KB a block (two blocks a CU).
-#include "gemm_pipe.h"
+#include "gemm_pipe_xform.h"
 
 namespace a2m {
 
-constexpr int kDownTA = 2 * 64 * kPipeLDK;    // an A stage: two units x 64 rows
-constexpr int kDownUnit = 32 * kPipeLDK;      // a V unit: 32 pairs
+constexpr int kDownTA = kXformTA;       // an A stage: two units x 64 rows (XformRows)
+constexpr int kDownUnit = kXformUnit;   // a V unit: 32 pairs
 constexpr int kDownLds = 2 * kDownTA + 8 * kDownUnit;
 static_assert(4 * 64 * 32 <= kDownLds, "the M planes reuse the stages");
-
-// V row of pair i (bits 1 and 2 swapped, the Winograd tile's map): a thread's pairs 2G, 2G + 1
-// (G = tid / 16) land 4 rows from those of G + 1, i.e. 16 banks on
-__device__ __forceinline__ int down_pair_row(int i) { return (i & ~6) | ((i & 2) << 1) | ((i & 4) >> 1); }
-
-// A: dense rows of K6 = 6 Ci; a step's tile is 64 rows x 64 k (the step's wn = 0 unit, then its
-// wn = 1 unit), four float4 per thread: q = 2 * unit + row half
-struct DownRows {
-  __amdgpu_buffer_rsrc_t rs;
-  uint32_t off[2];
-  int kq, lrow, knext, K6;
-  __device__ __forceinline__ void init(const Gather& g, int z, int row0, int R, int KK6, int tid, int kbeg6) {
-    rs = pipe_rsrc(g.base + (int64_t)z * g.bstride);
-    kq = (tid & 7) * 4;
-    lrow = tid >> 3;
-    K6 = KK6;
-    knext = kbeg6;
-#pragma unroll
-    for (int p = 0; p < 2; ++p) {
-      const int row = row0 + lrow + 32 * p;
-      off[p] = row < R ? (uint32_t)(row * g.sr0 + kbeg6 + kq) * 4u : kPipeOOB;
-    }
-  }
-  template <int Q>
-  __device__ __forceinline__ void load(float4 (&r)[4]) {
-    r[Q] = pipe_load(rs, knext < K6 ? off[Q & 1] + 4u * 32 * (Q >> 1) : kPipeOOB);
-    if (Q == 3) {
-      off[0] += 4u * 64;
-      off[1] += 4u * 64;
-      knext += 64;
-    }
-  }
-  template <int Q>
-  __device__ __forceinline__ void store(float* st, const float4 (&r)[4]) const {
-    *reinterpret_cast<float4*>(st + ((Q >> 1) * 64 + lrow + 32 * (Q & 1)) * kPipeLDK + kq) = r[Q];
-  }
-};
 
 // B: per chunk and channel half p the thread's x[t0 - 1], x[t0 .. t0 + 7], x[t0 + 8] of channel
 // kq + 16 p (t0 = 8 (tid / 16) within the tile's 128 input samples; the two outer elements read 0
@@ -96,7 +59,7 @@ struct DownX {
     off = valid ? (uint32_t)(b * g.sr0 + tt + ch * sk0) * 4u : kPipeOOB;
     offm = valid && tt > 0 ? off - 4u : kPipeOOB;
     offp = valid && tt + 8 < T ? off + 32u : kPipeOOB;
-    v0 = down_pair_row(2 * grp) * kPipeLDK + kq;
+    v0 = xform_pair_row(2 * grp) * kPipeLDK + kq;
   }
   template <int P>
   __device__ __forceinline__ void load(float (&r)[2][10]) {
@@ -154,7 +117,7 @@ __global__ __launch_bounds__(256) void gemm_pipe_kernel_down(GemmArgs args) {
   const int c0 = kbeg / 128;
   const int nch = __builtin_amdgcn_readfirstlane(kbeg < kend ? (kend - kbeg) / 128 : 0);
 
-  DownRows la;
+  XformRows la;
   la.init(args.A, batch, m0, args.M, 6 * Ci, tid, c0 * 192);
   DownX lx;
   lx.init(args.B, batch, n0, args.N, Ci, tid, c0 * 32);
@@ -245,43 +208,14 @@ __global__ __launch_bounds__(256) void gemm_pipe_kernel_down(GemmArgs args) {
   }
   if (cc < nch) chunk(P0(), cc);
 
-  __syncthreads();   // the M planes reuse the stages
-  // M planes [plane][row][pair] (pitch 32: a ds_write_b32's 32 lanes are one row's 32 pairs):
-  // 0 = M0, 1 = M1's odd-phase half, 2 = M1's even-phase half, 3 = M2
-  const int pair = down_pair_row(li);
-#pragma unroll
-  for (int q = 0; q < 16; ++q) {
-    const int row = wm * 32 + (q & 3) + 8 * (q >> 2) + 4 * lh;
-    lds[(wn * 192 + row) * 32 + pair] = acc0[q];
-    lds[((1 + wn) * 64 + row) * 32 + pair] = acc1[q];
-  }
-  __syncthreads();
-  // this lane's column n = wn * 32 + li of the y tile, in the accumulator layout of a wave that
-  // owns rows wm * 32 .. and columns wn * 32 ..: y[2i] = M0 + M1, y[2i + 1] = M2 + M1
-  floatx16 acc;
-  {
-    const int n = wn * 32 + li;
-    const bool odd = n & 1;
-    const float* const pm = lds + (n >> 1);
-#pragma unroll
-    for (int q = 0; q < 16; ++q) {
-      const int row = wm * 32 + (q & 3) + 8 * (q >> 2) + 4 * lh;
-      const float M1o = pm[(64 + row) * 32], M1e = pm[(128 + row) * 32];
-      const float Me = pm[((odd ? 192 : 0) + row) * 32];   // M2 (odd) or M0 (even)
-      acc[q] = Me + (M1o + M1e);
-    }
-  }
-  __syncthreads();   // the epilogues stage the tile through the same LDS
-  floatx16 accs[1][1];
-  accs[0][0] = acc;
-  if (args.vec4) pipe_epilogue_vec4(args, acc, lds, epr, args.partial != nullptr, zz, batch, m0, n0, tid, wm, wn, li, lh);
-  else tile_epilogue<BM, BN, 1, 1>(args, accs, lds, epr, args.partial != nullptr, zz, batch, m0, n0, tid, wm, wn, li, lh);
+  // M planes [plane][row][pair]: 0 = M0, 1 = M1's odd-phase half, 2 = M1's even-phase half, 3 = M2;
+  // y[2i] = M0 + M1, y[2i + 1] = M2 + M1 (Me: M2 odd, M0 even)
+  xform_epilogue(args, lds, epr, acc0, 3 * wn, acc1, 1 + wn,
+                 [](float M1o, float M1e, float Me, bool) { return Me + (M1o + M1e); },
+                 zz, batch, m0, n0, tid, wm, wn, li, lh);
   span_end(args.ts);
 }
 
-void launch_pipe_down(const GemmArgs& a, int batch, hipStream_t st) {
-  const dim3 grid((unsigned)cdiv(a.N, 64), (unsigned)cdiv(a.M, 64), (unsigned)(batch * a.splits));
-  hipLaunchKernelGGL(gemm_pipe_kernel_down, grid, dim3(256), 0, st, a);
-}
+void launch_pipe_down(const GemmArgs& a, int batch, hipStream_t st) { launch_xform<gemm_pipe_kernel_down>(a, batch, st); }
 
 }  // namespace a2m

@@ -11,64 +11,28 @@
 // all 32 pairs and the points wn and wn + 2: two accumulators, 32 MFMAs per 32-channel chunk (48
 // in the direct tile).  A chunk is two of gemm_pipe.h's k-steps (pipe_step): step 0 multiplies
 // points 0 / 1 into the waves' first accumulators, step 1 points 2 / 3 into their second.
-//   A: the packed U, [Co][Ci / 32][4][32], read as dense rows of 4 Ci; a step's tile is two points'
-//      64 x 32 (stages by step parity, [point][row][36]).
+//   A: the packed U, [Co][Ci / 32][4][32], read as dense rows of 4 Ci (XformRows); a step's tile is
+//      two points' 64 x 32 (stages by step parity, [point][row][36]).
 //   B: the chunk's x window is loaded once per thread as in the halo layout (4 consecutive t =
 //      two pairs of channels kq and kq + 16) plus x[t0 - 1] and x[t0 + 4], transformed in registers
 //      and stored as V[point][pair][36] (stages by chunk parity).  Pair i is stored at row
-//      wino_pair_row(i), which keeps the 32 lanes of a ds_write_b32 on distinct banks; lane li of a
-//      fragment read takes row li, so it computes pair wino_pair_row(li) (an involution).
+//      xform_pair_row(i) (gemm_pipe_xform.h), which keeps the 32 lanes of a ds_write_b32 on distinct
+//      banks; lane li of a fragment read takes row li, so it computes pair xform_pair_row(li) (an
+//      involution).
 // The operand work sits in the MFMA shadows in pipe_step's slices.  The epilogue writes the four
 // M planes to LDS, every lane rebuilds its accumulator of the 64x64 y tile in the MFMA C layout
 // and the tile's existing epilogues run unchanged (vec4 / scalar / m-contiguous / split-K slab:
 // the transform is linear, so slabs hold transformed outputs and splitk_reduce_kernel serves).
 // LDS: 2 x 18 KB A stages + 2 x 18 KB V stages = 72 KB a block (two blocks a CU).
-#include "gemm_pipe.h"
+#include "gemm_pipe_xform.h"
 
 namespace a2m {
 
-constexpr int kWinoTA = 2 * 64 * kPipeLDK;    // an A stage: two points x 64 rows
-constexpr int kWinoPlane = 32 * kPipeLDK;     // one point of a V stage: 32 pairs
+constexpr int kWinoTA = kXformTA;        // an A stage: two points x 64 rows (XformRows)
+constexpr int kWinoPlane = kXformUnit;   // one point of a V stage: 32 pairs
 constexpr int kWinoTV = 4 * kWinoPlane;
 constexpr int kWinoLds = 2 * kWinoTA + 2 * kWinoTV;
 static_assert(4 * 64 * 32 <= kWinoLds, "the M planes reuse the stages");
-
-// V stage row of pair i (bits 1 and 2 swapped): a thread's pairs 2G, 2G + 1 (G = tid / 16) land
-// 4 rows from those of G + 1, i.e. 16 banks on
-__device__ __forceinline__ int wino_pair_row(int i) { return (i & ~6) | ((i & 2) << 1) | ((i & 4) >> 1); }
-
-// A: dense rows of K4 = 4 Ci; a step's tile is 64 rows x 64 k (point 2s, then point 2s + 1), four
-// float4 per thread: q = 2 * point + row half
-struct WinoRows {
-  __amdgpu_buffer_rsrc_t rs;
-  uint32_t off[2];
-  int kq, lrow, knext, K4;
-  __device__ __forceinline__ void init(const Gather& g, int z, int row0, int R, int KK4, int tid, int kbeg4) {
-    rs = pipe_rsrc(g.base + (int64_t)z * g.bstride);
-    kq = (tid & 7) * 4;
-    lrow = tid >> 3;
-    K4 = KK4;
-    knext = kbeg4;
-#pragma unroll
-    for (int p = 0; p < 2; ++p) {
-      const int row = row0 + lrow + 32 * p;
-      off[p] = row < R ? (uint32_t)(row * g.sr0 + kbeg4 + kq) * 4u : kPipeOOB;
-    }
-  }
-  template <int Q>
-  __device__ __forceinline__ void load(float4 (&r)[4]) {
-    r[Q] = pipe_load(rs, knext < K4 ? off[Q & 1] + 4u * 32 * (Q >> 1) : kPipeOOB);
-    if (Q == 3) {
-      off[0] += 4u * 64;
-      off[1] += 4u * 64;
-      knext += 64;
-    }
-  }
-  template <int Q>
-  __device__ __forceinline__ void store(float* st, const float4 (&r)[4]) const {
-    *reinterpret_cast<float4*>(st + ((Q >> 1) * 64 + lrow + 32 * (Q & 1)) * kPipeLDK + kq) = r[Q];
-  }
-};
 
 // B: per chunk and channel half p the thread's x[t0 - 1], x[t0 .. t0 + 3], x[t0 + 4] of channel
 // kq + 16 p (t0 = the first of its 4 rows within the clip; the two outer elements read 0 at the
@@ -91,7 +55,7 @@ struct WinoX {
     off = valid ? (uint32_t)(b * g.sr0 + tt + ch * sk0) * 4u : kPipeOOB;
     offm = valid && tt > 0 ? off - 4u : kPipeOOB;
     offp = valid && tt + 4 < T ? off + 16u : kPipeOOB;
-    v0 = wino_pair_row(lrow >> 1) * kPipeLDK + kq;
+    v0 = xform_pair_row(lrow >> 1) * kPipeLDK + kq;
   }
   template <int P>
   __device__ __forceinline__ void load(float (&r)[2][6]) {
@@ -145,7 +109,7 @@ __global__ __launch_bounds__(256) void gemm_pipe_kernel_wino(GemmArgs args) {
   const int c0 = kbeg / 96;
   const int nch = __builtin_amdgcn_readfirstlane(kbeg < kend ? (kend - kbeg) / 96 : 0);
 
-  WinoRows la;
+  XformRows la;
   la.init(args.A, batch, m0, args.M, 4 * Ci, tid, c0 * 128);
   WinoX lx;
   lx.init(args.B, batch, n0, args.N, Ci, tid, c0 * 32);
@@ -208,42 +172,13 @@ __global__ __launch_bounds__(256) void gemm_pipe_kernel_wino(GemmArgs args) {
     });
   }
 
-  __syncthreads();   // the M planes reuse the stages
-  // M planes [point][row][pair] (pitch 32: a ds_write_b32's 32 lanes are one row's 32 pairs)
-  const int pair = wino_pair_row(li);
-#pragma unroll
-  for (int q = 0; q < 16; ++q) {
-    const int row = wm * 32 + (q & 3) + 8 * (q >> 2) + 4 * lh;
-    lds[(wn * 64 + row) * 32 + pair] = acc0[q];
-    lds[((wn + 2) * 64 + row) * 32 + pair] = acc1[q];
-  }
-  __syncthreads();
-  // this lane's column n = wn * 32 + li of the y tile, in the accumulator layout of a wave that
-  // owns rows wm * 32 .. and columns wn * 32 ..: y[2i] = M0 + M1 + M2, y[2i + 1] = M1 - M2 - M3
-  floatx16 acc;
-  {
-    const int n = wn * 32 + li;
-    const bool odd = n & 1;
-    const float* const pm = lds + (n >> 1);
-#pragma unroll
-    for (int q = 0; q < 16; ++q) {
-      const int row = wm * 32 + (q & 3) + 8 * (q >> 2) + 4 * lh;
-      const float M1 = pm[(64 + row) * 32], M2 = pm[(128 + row) * 32];
-      const float Me = pm[((odd ? 192 : 0) + row) * 32];   // M3 (odd) or M0 (even)
-      acc[q] = odd ? (M1 - M2) - Me : (Me + M1) + M2;
-    }
-  }
-  __syncthreads();   // the epilogues stage the tile through the same LDS
-  floatx16 accs[1][1];
-  accs[0][0] = acc;
-  if (args.vec4) pipe_epilogue_vec4(args, acc, lds, epr, args.partial != nullptr, zz, batch, m0, n0, tid, wm, wn, li, lh);
-  else tile_epilogue<BM, BN, 1, 1>(args, accs, lds, epr, args.partial != nullptr, zz, batch, m0, n0, tid, wm, wn, li, lh);
+  // M planes [point][row][pair]: y[2i] = M0 + M1 + M2, y[2i + 1] = M1 - M2 - M3 (Me: M3 odd, M0 even)
+  xform_epilogue(args, lds, epr, acc0, wn, acc1, wn + 2,
+                 [](float M1, float M2, float Me, bool odd) { return odd ? (M1 - M2) - Me : (Me + M1) + M2; },
+                 zz, batch, m0, n0, tid, wm, wn, li, lh);
   span_end(args.ts);
 }
 
-void launch_pipe_wino(const GemmArgs& a, int batch, hipStream_t st) {
-  const dim3 grid((unsigned)cdiv(a.N, 64), (unsigned)cdiv(a.M, 64), (unsigned)(batch * a.splits));
-  hipLaunchKernelGGL(gemm_pipe_kernel_wino, grid, dim3(256), 0, st, a);
-}
+void launch_pipe_wino(const GemmArgs& a, int batch, hipStream_t st) { launch_xform<gemm_pipe_kernel_wino>(a, batch, st); }
 
 }  // namespace a2m

@@ -219,6 +219,13 @@ static Plan launch_plan(int M, int N, int K, int batch, bool gathered, int prec,
   return p;
 }
 
+void route_out(const GemmRoute& r, int32_t out[8]) {
+  const int32_t o[8] = {r.kind, r.tile, r.bk, r.splits, r.kchunk, r.ma, r.mb,
+                        (r.vec4 ? 1 : 0) | (r.mcontig ? 2 : 0) | (r.halo ? 4 : 0) | (r.reduce ? 8 : 0) |
+                            (r.xform == XFORM_WINO ? 16 : 0) | (r.xform == XFORM_DOWN ? 32 : 0)};
+  for (int i = 0; i < 8; ++i) out[i] = o[i];
+}
+
 size_t split_ws_bytes(const GemmRoute& r, int M, int N, int batch) {
   return (size_t)r.splits * batch * M * (size_t)N * sizeof(float);
 }
@@ -315,39 +322,28 @@ static PipeOperands pipe_operands(const Gather& A, const Gather& B, int ma, int 
   return {false, false, 0, 0};
 }
 
-// Shape classes of requested, eligible launches that stay on the direct tile because it measured
-// faster there: blocks = 64x64 tiles x batch of the launch (before split-K), K = 3 Ci.  A launch
-// outside every class takes the Winograd tile.  The table is empty: all six shapes of the bench
+// Shape classes of requested, eligible launches that stay on the route without the request because
+// it measured faster there: blocks = 64x64 tiles x batch of the launch (before split-K), K the
+// direct conv's.  A launch outside every class of its tile's table takes the tile.
+struct DirectRule {
+  int64_t min_blocks, max_blocks;
+  int min_k, max_k;
+};
+// Winograd (K = 3 Ci) against the direct tap tile.  The table is empty: all six shapes of the bench
 // step measured faster on the Winograd tile, alone and in the step's kernel trace -- the UNet's
 // five (512-1024 blocks, K 768-6144) by 9-19 %, the decoders' one-block-per-CU launch (256 blocks,
 // K 768) by 5 % alone and 11 % in the trace (profiles/wino_conv.txt).
-struct WinoDirectRule {
-  int64_t min_blocks, max_blocks;
-  int min_k, max_k;
-};
-static const std::vector<WinoDirectRule> kWinoDirect = {};
-bool wino_rule(int M, int N, int K, int batch) {
+static const std::vector<DirectRule> kWinoDirect = {};
+// down-sampling (K = 4 Ci) against the im2col route (im2col1d_kernel and the dense tile).  The
+// table is empty: both shapes of the bench step measured faster on the down-sampling tile, alone
+// and in the step's kernel trace (profiles/down_conv.txt).
+static const std::vector<DirectRule> kDownDirect = {};
+bool xform_rule(Xform xform, int M, int N, int K, int batch) {
   const int64_t blocks = cdiv(M, 64) * cdiv(N, 64) * (int64_t)batch;
-  // experiments: launches of fewer blocks stay on the direct tile (read once, like A2M_GEMM_PLAN_RULES)
-  static const int min_blocks = env_int("A2M_WINO_MIN_BLOCKS", 0);
-  if (blocks < min_blocks) return false;
-  for (const WinoDirectRule& d : kWinoDirect)
-    if (blocks >= d.min_blocks && blocks <= d.max_blocks && K >= d.min_k && K <= d.max_k) return false;
-  return true;
-}
-
-// Shape classes of requested, eligible 4-tap stride-2 launches that stay on the im2col route
-// (im2col1d_kernel and the dense tile) because it measured faster there; blocks and K (= 4 Ci) as
-// in kWinoDirect.  The table is empty: both shapes of the bench step measured faster on the
-// down-sampling tile, alone and in the step's kernel trace (profiles/down_conv.txt).
-struct DownDirectRule {
-  int64_t min_blocks, max_blocks;
-  int min_k, max_k;
-};
-static const std::vector<DownDirectRule> kDownDirect = {};
-bool down_rule(int M, int N, int K, int batch) {
-  const int64_t blocks = cdiv(M, 64) * cdiv(N, 64) * (int64_t)batch;
-  for (const DownDirectRule& d : kDownDirect)
+  // experiments: Winograd launches of fewer blocks stay on the direct tile (read once, like A2M_GEMM_PLAN_RULES)
+  static const int wino_min_blocks = env_int("A2M_WINO_MIN_BLOCKS", 0);
+  if (xform == XFORM_WINO && blocks < wino_min_blocks) return false;
+  for (const DirectRule& d : xform == XFORM_WINO ? kWinoDirect : kDownDirect)
     if (blocks >= d.min_blocks && blocks <= d.max_blocks && K >= d.min_k && K <= d.max_k) return false;
   return true;
 }
@@ -379,8 +375,8 @@ GemmRoute gemm_route(const Gather& A, const Gather& B, const Epilogue& E, int M,
   // of 32 channels) is the planner's for the direct conv's M x N x 4 Ci on the pipelined 64x64
   // tile.  Refused: the caller's operands are those of no other kernel (A is the packed U), so
   // a2m_conv1d_down_* take a2m_conv1d_fwd_f32's route with its operands instead.
-  if (cfg.down && prec == 0 && cfg.pipe_override != 0 &&
-      down_operands(A, B, E, ma, M, N, K) && down_rule(M, N, K, batch)) {
+  if (cfg.xform == XFORM_DOWN && prec == 0 && cfg.pipe_override != 0 &&
+      down_operands(A, B, E, ma, M, N, K) && xform_rule(XFORM_DOWN, M, N, K, batch)) {
     // The planner's table is the direct tile's, which splits K to put two blocks on a CU.  This
     // tile issues three quarters of the MFMAs, and a launch that already has a block for every CU
     // measured as fast or faster at one split, without slabs or a reduce launch (512x2048x2048:
@@ -398,7 +394,7 @@ GemmRoute gemm_route(const Gather& A, const Gather& B, const Epilogue& E, int M,
       r.ks = 1;
       r.kind = A2M_GEMM_KIND_PIPE;
       r.pipe_mb = mb; r.pipe_ma = 0; r.pipe_nt = 0;
-      r.down = true;
+      r.xform = XFORM_DOWN;
       return r;
     }
   }
@@ -436,9 +432,10 @@ GemmRoute gemm_route(const Gather& A, const Gather& B, const Epilogue& E, int M,
   // halo-layout launches (3 taps, pad 1, clips of T >= 16) with whole 32-channel chunks and dense
   // packed weights of 4 Ci floats a row, where the rule table keeps the shape on it.  The plan
   // (tile, splits, kchunk) is the direct conv's.  Refused: exactly the route without the request.
-  r.wino = cfg.wino && pipe && prec == 0 && r.halo && po.ma == 0 && K % 96 == 0 && !r.interp &&
-           A.sr0 == 4 * (K / 3) && pipe_below((int64_t)(M - 1) * A.sr0 + 4 * (K / 3)) &&
-           wino_rule(M, N, K, batch);
+  if (cfg.xform == XFORM_WINO && pipe && prec == 0 && r.halo && po.ma == 0 && K % 96 == 0 && !r.interp &&
+      A.sr0 == 4 * (K / 3) && pipe_below((int64_t)(M - 1) * A.sr0 + 4 * (K / 3)) &&
+      xform_rule(XFORM_WINO, M, N, K, batch))
+    r.xform = XFORM_WINO;
   if (pipe) {
     r.kind = A2M_GEMM_KIND_PIPE;
     r.pipe_mb = po.mb; r.pipe_ma = po.ma;

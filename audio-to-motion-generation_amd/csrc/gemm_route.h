@@ -13,8 +13,7 @@ struct RouteConfig {
   int pair_override;    // a2m_convt_pair_override: -1 default (gemm_pair's fill rule), 0 never, 1 whenever eligible
   int override_tile, override_split;   // a2m_gemm_plan_override (tuning)
   int halo_on;          // A2M_GEMM_HALO
-  int wino;             // this launch asks for the Winograd F(2,3) tile (a2m_conv1d_wino_*; not process-wide)
-  int down;             // this launch asks for the Toom-Cook F(2,2) down-sampling tile (a2m_conv1d_down_*; not process-wide)
+  Xform xform;          // this launch asks for a transform tile (a2m_conv1d_wino_*, a2m_conv1d_down_*; not process-wide)
 };
 
 struct GemmRoute {
@@ -24,8 +23,7 @@ struct GemmRoute {
   int pipe_mb, pipe_nt, pipe_ma;   // template arguments of the pipelined kernel (kind PIPE)
   int ks;                     // gemm_tile wave groups (1 or 2)
   bool halo, vec4, mcontig, reduce, interp;
-  bool wino;                  // kind PIPE as gemm_pipe_kernel_wino: A is the Winograd-packed weights
-  bool down;                  // kind PIPE as gemm_pipe_kernel_down: A is the weights packed by a2m_conv1d_down_pack_f32
+  Xform xform;                // kind PIPE as gemm_pipe_kernel_wino / gemm_pipe_kernel_down: A is that tile's packed weights
 };
 
 // Pure: no HIP call, no allocation, no mutable file-scope state (A2M_GEMM_PLAN_RULES is parsed
@@ -34,6 +32,9 @@ GemmRoute gemm_route(const Gather& A, const Gather& B, const Epilogue& E, int M,
                      int force_split, const RouteConfig& cfg);
 
 RouteConfig route_config();   // the current switches (gemm.hip)
+// a route as the a2m_*_route queries report it: {kind, tile, bk, splits, kchunk, ma, mb, flags} with flags
+// 1 vec4, 2 m-contiguous, 4 halo, 8 reduce, 16 the Winograd tile, 32 the down-sampling tile
+void route_out(const GemmRoute& r, int32_t out[8]);
 
 int gemm_bk(int prec);
 // slab workspace of a split route: [splits][batch][M][N] for the reduce kernel
@@ -42,10 +43,8 @@ size_t split_ws_bytes(const GemmRoute& r, int M, int N, int batch);
 size_t gemm_ws_bytes(int M, int N, int K, int batch, const RouteConfig& cfg);
 // whether A2M_GEMM_PLAN_RULES fixes more than one split for the shape
 bool plan_rule_splits(int M, int N, int K);
-// whether the per-shape rule table keeps a requested, eligible launch on the Winograd tile (false:
-// the direct tile measured faster for the shape class)
-bool wino_rule(int M, int N, int K, int batch);
-// the same for the down-sampling tile (false: the im2col route measured faster)
-bool down_rule(int M, int N, int K, int batch);
+// whether the tile's per-shape rule table keeps a requested, eligible launch on it (false: the
+// route without the request measured faster for the shape class)
+bool xform_rule(Xform xform, int M, int N, int K, int batch);
 
 }  // namespace a2m

@@ -595,6 +595,72 @@ static int conv2d_nhwc_gemm(const float* x, int B, int Ci, int H, int W, const f
   return gemm(A, Bg, E, Co, B * Hout * Wn, Ci * kh * kw, 1, ws, ws_bytes, st);
 }
 
+// ---- the conv1d front: one launch as the engine sees it, and builders that each state one part once
+struct ConvProblem {
+  Gather A, B;
+  Epilogue E;
+  int N, K;
+};
+
+// C[co][n = b * T + t] -> y[b][co][t] at strides ys_b, ys_c, ys_t
+static Epilogue conv1d_epi(Epilogue E, int T, int64_t ys_b, int64_t ys_c, int64_t ys_t) {
+  E.N1 = 1; E.N2 = T; E.so0 = (int)ys_b; E.so1 = 0; E.so2 = (int)ys_t; E.som = (int)ys_c;
+  return E;
+}
+
+// the tap-chunked operand (loader mode 5) of a stride-1 conv1d of `taps` taps over t-contiguous
+// x [B][Ci][T], the first tap at input shift cw; xs_g: the stride between a group's problems
+static Gather tap_gather(const float* x, int64_t xs_g, int64_t xs_b, int64_t xs_c, int T, int taps, int cw) {
+  Gather g{};
+  g.base = x; g.bstride = xs_g;
+  g.sr0 = (int)xs_b; g.R1 = 1; g.R2 = T; g.sk0 = (int)xs_c;
+  g.K1 = g.K2 = 1; g.divh = g.divw = 1; g.Lh = g.Lw = 1;
+  g.cw = cw; g.tapconv = taps;
+  return g;
+}
+
+// the plain gather of a conv1d: rows n = (b, t), k = (ci, tap) -> x[b][ci][t * stride - pad + tap]
+static Gather conv1d_gather(const float* x, int64_t xs_b, int64_t xs_c, int64_t xs_t, int Tin, int Tout, int ks,
+                            int stride, int pad) {
+  Gather g{};
+  g.base = x; g.bstride = 0;
+  g.sr0 = (int)xs_b; g.R1 = 1; g.R2 = Tout; g.ar1 = 0; g.ar2 = stride;
+  g.sk0 = (int)xs_c; g.K1 = 1; g.K2 = ks; g.bk1 = 0; g.bk2 = 1;
+  g.ch = 0; g.cw = -pad; g.divh = g.divw = 1; g.Lh = 1; g.Lw = Tin;
+  g.sh = 0; g.sw = (int)xs_t;
+  g.kcontig = (ks == 1 && xs_c == 1) ? 1 : 0;
+  return g;
+}
+
+// whether a2m_conv1d_fwd_f32 takes the explicit im2col (N x K matrix in the workspace head, then a
+// dense x dense GEMM)
+static bool conv1d_takes_im2col(int Co, int ks, int stride, int64_t xs_t, int64_t N, int64_t K) {
+  return ks > 1 && ks <= 8 && stride <= 2 && Co >= 128 && xs_t == 1 && K % 4 == 0 && N * K < (1LL << 31);
+}
+
+// The GEMM of a2m_conv1d_fwd_f32 (E: the conv's epilogue).  col: the im2col matrix where
+// conv1d_takes_im2col; a route query has none and passes null -- a stand-in of the workspace's
+// alignment then serves, since a route inspects pointers for alignment only.
+static ConvProblem conv1d_fwd_problem(const float* x, int64_t xs_b, int64_t xs_c, int64_t xs_t, int B, int Ci, int Tin,
+                                      const float* w, int Co, int ks, int stride, int pad, const float* col,
+                                      const Epilogue& E) {
+  const int Tout = (Tin + 2 * pad - ks) / stride + 1;
+  const int64_t K = (int64_t)Ci * ks, N = (int64_t)B * Tout;
+  ConvProblem p;
+  p.N = (int)N; p.K = (int)K; p.E = E;
+  p.A = dense_rk(w, (int)K);
+  if (conv1d_takes_im2col(Co, ks, stride, xs_t, N, K)) {
+    p.B = dense_rk(col ? col : reinterpret_cast<const float*>(uintptr_t(256)), (int)K);
+  } else if (ks == 1 && pad == 0 && stride == 1 && xs_b == (int64_t)Tin * xs_t) {
+    // rows n = b*T + t are uniformly strided: plain [N][Ci] (k-major when xs_c == 1)
+    p.B = xs_c == 1 ? dense_rk(x, (int)xs_t) : dense_kr(x, (int)xs_c);
+    if (xs_c != 1) p.B.sr0 = (int)xs_t;
+  } else {
+    p.B = conv1d_gather(x, xs_b, xs_c, xs_t, Tin, Tout, ks, stride, pad);
+  }
+  return p;
+}
+
 extern "C" {
 
 int a2m_conv1d_fwd_f32(const float* x, int64_t xs_b, int64_t xs_c, int64_t xs_t, int32_t B,
@@ -612,47 +678,29 @@ int a2m_conv1d_fwd_f32(const float* x, int64_t xs_b, int64_t xs_c, int64_t xs_t,
   A2M_CHECK_ARG(fits32(xs_b) && fits32(xs_c) && fits32(xs_t) && fits32(ys_b) && fits32(ys_c) &&
                     fits32(ys_t) && fits32((int64_t)B * xs_b) && fits32((int64_t)B * ys_b),
                 "conv1d: tensor too large for 32-bit offsets");
-  Gather A = dense_rk(w, Ci * ks);
-  Gather Bg{};
   const int64_t K = (int64_t)Ci * ks, N = (int64_t)B * Tout;
-  if (ks > 1 && ks <= 8 && stride <= 2 && Co >= 128 && xs_t == 1 && K % 4 == 0 &&
-      N * K < (1LL << 31)) {
-    // explicit im2col into the workspace head, then a dense x dense GEMM
-    const size_t col_bytes = ((size_t)(N * K) * sizeof(float) + 255) & ~size_t(255);
+  hipStream_t st = as_stream(stream);
+  float* col = nullptr;
+  size_t col_bytes = 0;
+  if (conv1d_takes_im2col(Co, ks, stride, xs_t, N, K)) {
+    col_bytes = ((size_t)(N * K) * sizeof(float) + 255) & ~size_t(255);
     const size_t need = col_bytes + gemm_ws_bytes(Co, (int)N, (int)K, 1);
     if (!ws || ws_bytes < need) {
       set_error("conv1d: workspace too small (%zu < %zu bytes)", ws_bytes, need);
       return A2M_EWS;
     }
-    float* col = static_cast<float*>(ws);
-    hipStream_t st = as_stream(stream);
+    col = static_cast<float*>(ws);
     // 16 channels a block, blocks grouped per XCD (32 channels measured alike, tools/ab_i2c.sh)
     const int n_rows = B * (int)cdiv(Tout, I2C_T), n_ct = (int)cdiv(Ci, 16);
     const unsigned blocks = (unsigned)(8 * n_ct * cdiv(n_rows, 8));
     hipLaunchKernelGGL(im2col1d_kernel<16>, dim3(blocks), dim3(256), 0, st, x, xs_b, xs_c, Ci, Tin,
                        Tout, ks, stride, pad, n_rows, n_ct, 1, col);
     A2M_LAUNCH_CHECK();
-    Bg = dense_rk(col, (int)K);
-    Epilogue E = epi_bn(y, bias, bn_w, bn_b, bn_rm, bn_rv, bn_eps, act, slope);
-    E.N1 = 1; E.N2 = Tout; E.so0 = (int)ys_b; E.so1 = 0; E.so2 = (int)ys_t; E.som = (int)ys_c;
-    return gemm(A, Bg, E, Co, (int)N, (int)K, 1, static_cast<char*>(ws) + col_bytes,
-                ws_bytes - col_bytes, st);
   }
-  if (ks == 1 && pad == 0 && stride == 1 && xs_b == (int64_t)Tin * xs_t) {
-    // rows n = b*T + t are uniformly strided: plain [N][Ci] (k-major when xs_c == 1)
-    Bg = xs_c == 1 ? dense_rk(x, (int)xs_t) : dense_kr(x, (int)xs_c);
-    if (xs_c != 1) Bg.sr0 = (int)xs_t;
-  } else {
-    Bg.base = x; Bg.bstride = 0;
-    Bg.sr0 = (int)xs_b; Bg.R1 = 1; Bg.R2 = Tout; Bg.ar1 = 0; Bg.ar2 = stride;
-    Bg.sk0 = (int)xs_c; Bg.K1 = 1; Bg.K2 = ks; Bg.bk1 = 0; Bg.bk2 = 1;
-    Bg.ch = 0; Bg.cw = -pad; Bg.divh = Bg.divw = 1; Bg.Lh = 1; Bg.Lw = Tin;
-    Bg.sh = 0; Bg.sw = (int)xs_t;
-    Bg.kcontig = (ks == 1 && xs_c == 1) ? 1 : 0;
-  }
-  Epilogue E = epi_bn(y, bias, bn_w, bn_b, bn_rm, bn_rv, bn_eps, act, slope);
-  E.N1 = 1; E.N2 = Tout; E.so0 = (int)ys_b; E.so1 = 0; E.so2 = (int)ys_t; E.som = (int)ys_c;
-  return gemm(A, Bg, E, Co, B * Tout, Ci * ks, 1, ws, ws_bytes, as_stream(stream));
+  const ConvProblem p = conv1d_fwd_problem(
+      x, xs_b, xs_c, xs_t, B, Ci, Tin, w, Co, ks, stride, pad, col,
+      conv1d_epi(epi_bn(y, bias, bn_w, bn_b, bn_rm, bn_rv, bn_eps, act, slope), Tout, ys_b, ys_c, ys_t));
+  return gemm(p.A, p.B, p.E, Co, p.N, p.K, 1, static_cast<char*>(ws) + col_bytes, ws_bytes - col_bytes, st);
 }
 
 int a2m_convt1d_packed_fwd_f32(const float* x, int64_t xs_b, int64_t xs_c, int32_t B, int32_t Ci,
@@ -684,8 +732,7 @@ int a2m_convt1d_packed_fwd_f32(const float* x, int64_t xs_b, int64_t xs_c, int32
     if (ntap == 0) {  // this phase only gets the bias / BN / act of zero
       Gather Az = dense_rk(packed, 1);
       Gather Bz = dense_rk(x, 1);
-      Epilogue E = epi_bn(yr, bias, bn_w, bn_b, bn_rm, bn_rv, bn_eps, act, slope);
-      E.N1 = 1; E.N2 = nu; E.so0 = (int)ys_b; E.so2 = stride; E.som = (int)ys_c;
+      const Epilogue E = conv1d_epi(epi_bn(yr, bias, bn_w, bn_b, bn_rm, bn_rv, bn_eps, act, slope), nu, ys_b, ys_c, stride);
       int rc = gemm(Az, Bz, E, Co, B * nu, 0, 1, nullptr, 0, st);
       if (rc) return rc;
       continue;
@@ -696,8 +743,7 @@ int a2m_convt1d_packed_fwd_f32(const float* x, int64_t xs_b, int64_t xs_c, int32
     Bg.base = x; Bg.sr0 = (int)xs_b; Bg.R1 = nu; Bg.R2 = 1; Bg.ar1 = 1; Bg.ar2 = 0;
     Bg.K1 = ntap; Bg.K2 = Ci; Bg.sk0 = 0; Bg.bk1 = -1; Bg.bk2 = 1; Bg.ch = off0; Bg.cw = 0;
     Bg.divh = Bg.divw = 1; Bg.Lh = Tin; Bg.Lw = Ci; Bg.sh = 1; Bg.sw = (int)xs_c; Bg.kcontig = 0;
-    Epilogue E = epi_bn(yr, bias, bn_w, bn_b, bn_rm, bn_rv, bn_eps, act, slope);
-    E.N1 = 1; E.N2 = nu; E.so0 = (int)ys_b; E.so2 = stride; E.som = (int)ys_c;
+    const Epilogue E = conv1d_epi(epi_bn(yr, bias, bn_w, bn_b, bn_rm, bn_rv, bn_eps, act, slope), nu, ys_b, ys_c, stride);
     int rc = gemm(A, Bg, E, Co, B * nu, ntap * Ci, 1, ws, ws_bytes, st);
     if (rc) return rc;
     off += (size_t)Co * ntap * Ci;
@@ -720,37 +766,6 @@ int a2m_conv1d_tap_pack_f32(const float* w, int32_t Co, int32_t Ci, int32_t ks, 
 
 int32_t a2m_conv1d_tap_chunk(void) { return gemm_k_tile(); }
 
-int a2m_conv1d_tap_fwd_f32(const float* x, int64_t xs_b, int64_t xs_c, int32_t B, int32_t Ci,
-                           int32_t T, const float* packed, int32_t chunk, const float* bias,
-                           int32_t Co, int32_t ks, int32_t pad, const float* bn_w,
-                           const float* bn_b, const float* bn_rm, const float* bn_rv, float bn_eps,
-                           int32_t act, float slope, float* y, int64_t ys_b, int64_t ys_c,
-                           int64_t ys_t, void* ws, size_t ws_bytes, void* stream) {
-  A2M_CHECK_ARG(x && packed && y, "conv1d_tap: null pointer");
-  A2M_CHECK_ARG(B > 0 && Ci > 0 && Co > 0 && ks > 1 && 2 * pad == ks - 1,
-                "conv1d_tap: bad shape B=%d Ci=%d Co=%d k=%d p=%d (stride 1, same padding)", B, Ci,
-                Co, ks, pad);
-  A2M_CHECK_ARG(chunk == gemm_k_tile() && Ci % chunk == 0,
-                "conv1d_tap: weights packed in %d-channel chunks, the engine's k-tile is %d (Ci=%d)",
-                chunk, gemm_k_tile(), Ci);
-  A2M_CHECK_ARG(T > 0 && T % 4 == 0 && 64 % T == 0 && pad < T,
-                "conv1d_tap: clip length %d must divide the 64-row tile and be a multiple of 4", T);
-  A2M_CHECK_ARG(fits32(xs_b) && fits32(xs_c) && fits32((int64_t)B * xs_b) &&
-                    fits32((int64_t)B * ys_b) && fits32(ys_c) && fits32(ys_t),
-                "conv1d_tap: tensor too large for 32-bit offsets");
-  A2M_CHECK_ARG((reinterpret_cast<uintptr_t>(x) % 16) == 0 && xs_b % 4 == 0 && xs_c % 4 == 0,
-                "conv1d_tap: x rows must be 16-byte aligned");
-  Gather A = dense_rk(packed, Ci * ks);
-  Gather Bg{};
-  Bg.base = x; Bg.bstride = 0;
-  Bg.sr0 = (int)xs_b; Bg.R1 = 1; Bg.R2 = T; Bg.sk0 = (int)xs_c;
-  Bg.K1 = Bg.K2 = 1; Bg.divh = Bg.divw = 1; Bg.Lh = Bg.Lw = 1;
-  Bg.cw = -pad; Bg.tapconv = ks;
-  Epilogue E = epi_bn(y, bias, bn_w, bn_b, bn_rm, bn_rv, bn_eps, act, slope);
-  E.N1 = 1; E.N2 = T; E.so0 = (int)ys_b; E.so1 = 0; E.so2 = (int)ys_t; E.som = (int)ys_c;
-  return gemm(A, Bg, E, Co, B * T, Ci * ks, 1, ws, ws_bytes, as_stream(stream));
-}
-
 int a2m_conv1d_tap_group_fwd_f32(const float* x, int64_t xs_g, int64_t xs_b, int64_t xs_c, int32_t G,
                                  int32_t B, int32_t Ci, int32_t T, const float* packed, int64_t w_gs,
                                  int32_t chunk, const float* bias, int32_t Co, int32_t ks, int32_t pad,
@@ -758,55 +773,62 @@ int a2m_conv1d_tap_group_fwd_f32(const float* x, int64_t xs_g, int64_t xs_b, int
                                  const float* bn_rv, float bn_eps, int32_t act, float slope, float* y,
                                  int64_t ys_g, int64_t ys_b, int64_t ys_c, int64_t ys_t, void* ws,
                                  size_t ws_bytes, void* stream) {
-  A2M_CHECK_ARG(x && packed && y && G > 0, "conv1d_tap_group: null pointer / G=%d", G);
+  A2M_CHECK_ARG(x && packed && y && G > 0, "conv1d_tap: null pointer / G=%d", G);
   A2M_CHECK_ARG(B > 0 && Ci > 0 && Co > 0 && ks > 1 && 2 * pad == ks - 1,
-                "conv1d_tap_group: bad shape B=%d Ci=%d Co=%d k=%d p=%d (stride 1, same padding)", B,
-                Ci, Co, ks, pad);
+                "conv1d_tap: bad shape B=%d Ci=%d Co=%d k=%d p=%d (stride 1, same padding)", B, Ci, Co, ks, pad);
   A2M_CHECK_ARG(chunk == gemm_k_tile() && Ci % chunk == 0,
-                "conv1d_tap_group: weights packed in %d-channel chunks, the engine's k-tile is %d (Ci=%d)",
+                "conv1d_tap: weights packed in %d-channel chunks, the engine's k-tile is %d (Ci=%d)",
                 chunk, gemm_k_tile(), Ci);
   A2M_CHECK_ARG(T > 0 && T % 4 == 0 && 64 % T == 0 && pad < T,
-                "conv1d_tap_group: clip length %d must divide the 64-row tile and be a multiple of 4", T);
+                "conv1d_tap: clip length %d must divide the 64-row tile and be a multiple of 4", T);
   A2M_CHECK_ARG(fits32(xs_b) && fits32(xs_c) && fits32((int64_t)B * xs_b) && fits32((int64_t)B * ys_b) &&
-                    fits32(ys_c) && fits32(ys_t) && ys_g != 0 && w_gs >= (int64_t)Co * Ci * ks,
-                "conv1d_tap_group: strides");
+                    fits32(ys_c) && fits32(ys_t) && (G == 1 || (ys_g != 0 && w_gs >= (int64_t)Co * Ci * ks)),
+                "conv1d_tap: strides / tensor too large for 32-bit offsets");
   A2M_CHECK_ARG((reinterpret_cast<uintptr_t>(x) % 16) == 0 && xs_b % 4 == 0 && xs_c % 4 == 0 &&
-                    xs_g % 4 == 0 && w_gs % 4 == 0 && (reinterpret_cast<uintptr_t>(packed) % 16) == 0,
-                "conv1d_tap_group: x rows / packed weights must be 16-byte aligned");
-  Gather A = dense_rk(packed, Ci * ks, w_gs);
-  Gather Bg{};
-  Bg.base = x; Bg.bstride = xs_g;
-  Bg.sr0 = (int)xs_b; Bg.R1 = 1; Bg.R2 = T; Bg.sk0 = (int)xs_c;
-  Bg.K1 = Bg.K2 = 1; Bg.divh = Bg.divw = 1; Bg.Lh = Bg.Lw = 1;
-  Bg.cw = -pad; Bg.tapconv = ks;
-  Epilogue E = epi_bn(y, bias, bn_w, bn_b, bn_rm, bn_rv, bn_eps, act, slope);
-  E.N1 = 1; E.N2 = T; E.so0 = (int)ys_b; E.so1 = 0; E.so2 = (int)ys_t; E.som = (int)ys_c;
+                    (G == 1 || (xs_g % 4 == 0 && w_gs % 4 == 0 && (reinterpret_cast<uintptr_t>(packed) % 16) == 0)),
+                "conv1d_tap: x rows (and a group's packed weights) must be 16-byte aligned");
+  Epilogue E = conv1d_epi(epi_bn(y, bias, bn_w, bn_b, bn_rm, bn_rv, bn_eps, act, slope), T, ys_b, ys_c, ys_t);
   E.bstride = ys_g; E.pstride = Co;
-  return gemm(A, Bg, E, Co, B * T, Ci * ks, G, ws, ws_bytes, as_stream(stream));
+  return gemm(dense_rk(packed, Ci * ks, w_gs), tap_gather(x, xs_g, xs_b, xs_c, T, ks, -pad), E, Co, B * T, Ci * ks, G,
+              ws, ws_bytes, as_stream(stream));
 }
 
-int a2m_conv1d_wino_pack_f32(const float* w, int32_t Co, int32_t Ci, float* packed, void* stream) {
-  A2M_CHECK_ARG(w && packed && Co > 0 && Ci > 0 && Ci % 32 == 0, "conv1d_wino_pack: bad args Co=%d Ci=%d (Ci %% 32)",
-                Co, Ci);
-  A2M_CHECK_ARG(fits32((int64_t)Co * Ci * 4), "conv1d_wino_pack: too large");
-  hipLaunchKernelGGL(conv1d_wino_pack_kernel, dim3((unsigned)std::min<int64_t>(cdiv((int64_t)Co * Ci, 256), 8192)),
-                     dim3(256), 0, as_stream(stream), w, Co, Ci, packed);
+int a2m_conv1d_tap_fwd_f32(const float* x, int64_t xs_b, int64_t xs_c, int32_t B, int32_t Ci,
+                           int32_t T, const float* packed, int32_t chunk, const float* bias,
+                           int32_t Co, int32_t ks, int32_t pad, const float* bn_w,
+                           const float* bn_b, const float* bn_rm, const float* bn_rv, float bn_eps,
+                           int32_t act, float slope, float* y, int64_t ys_b, int64_t ys_c,
+                           int64_t ys_t, void* ws, size_t ws_bytes, void* stream) {
+  return a2m_conv1d_tap_group_fwd_f32(x, 0, xs_b, xs_c, 1, B, Ci, T, packed, 0, chunk, bias, Co, ks, pad, bn_w, bn_b,
+                                      bn_rm, bn_rv, bn_eps, act, slope, y, 0, ys_b, ys_c, ys_t, ws, ws_bytes, stream);
+}
+
+// a2m_conv1d_wino_pack_f32 / a2m_conv1d_down_pack_f32: one thread per (co, ci) writes its `points` floats
+static int point_pack(const char* who, void (*kernel)(const float*, int, int, float*), int points, const float* w,
+                      int32_t Co, int32_t Ci, float* packed, void* stream) {
+  A2M_CHECK_ARG(w && packed && Co > 0 && Ci > 0 && Ci % 32 == 0, "%s: bad args Co=%d Ci=%d (Ci %% 32)", who, Co, Ci);
+  A2M_CHECK_ARG(fits32((int64_t)Co * Ci * points), "%s: too large", who);
+  hipLaunchKernelGGL(kernel, dim3((unsigned)std::min<int64_t>(cdiv((int64_t)Co * Ci, 256), 8192)), dim3(256), 0,
+                     as_stream(stream), w, Co, Ci, packed);
   A2M_LAUNCH_CHECK();
   return A2M_OK;
 }
 
-// the operands of a 3-tap pad-1 stride-1 conv1d over G problems as the engine sees them: A the
-// packed weights (wino: 4 Ci floats a row, else the tap-chunked 3 Ci), B the tap conv of x
-struct WinoProblem {
-  Gather A, B;
-  Epilogue E;
-};
-static int wino_problem(WinoProblem& p, const float* x, int64_t xs_g, int64_t xs_b, int64_t xs_c, int32_t G,
-                        int32_t B, int32_t Ci, int32_t T, const float* packed, int64_t w_gs, int32_t wino,
-                        const float* bias, int32_t Co, const float* bn_w, const float* bn_b, const float* bn_rm,
-                        const float* bn_rv, float bn_eps, int32_t act, float slope, const float* res, float* y,
-                        int64_t ys_g, int64_t ys_b, int64_t ys_c, int64_t ys_t) {
-  A2M_CHECK_ARG(x && packed && y && G > 0, "conv1d_wino: null pointer / G=%d", G);
+int a2m_conv1d_wino_pack_f32(const float* w, int32_t Co, int32_t Ci, float* packed, void* stream) {
+  return point_pack("conv1d_wino_pack", conv1d_wino_pack_kernel, 4, w, Co, Ci, packed, stream);
+}
+
+int a2m_conv1d_down_pack_f32(const float* w, int32_t Co, int32_t Ci, float* packed, void* stream) {
+  return point_pack("conv1d_down_pack", conv1d_down_pack_kernel, 6, w, Co, Ci, packed, stream);
+}
+
+// a2m_conv1d_wino_*'s argument checks and the operands of a 3-tap pad-1 stride-1 conv1d over G
+// problems: A the packed weights (wino: 4 Ci floats a row, else the tap-chunked 3 Ci), B the tap
+// conv of x, E (the caller's bias / BN / activation) addressed as the conv's output
+static int wino_problem(ConvProblem& p, const float* x, int64_t xs_g, int64_t xs_b, int64_t xs_c, int32_t G,
+                        int32_t B, int32_t Ci, int32_t T, const float* packed, int64_t w_gs, int32_t wino, int32_t Co,
+                        const Epilogue& E, int64_t ys_g, int64_t ys_b, int64_t ys_c, int64_t ys_t) {
+  A2M_CHECK_ARG(x && packed && E.out && G > 0, "conv1d_wino: null pointer / G=%d", G);
   A2M_CHECK_ARG(B > 0 && Ci > 0 && Co > 0 && T > 0, "conv1d_wino: bad shape B=%d Ci=%d Co=%d T=%d", B, Ci, Co, T);
   const int kw = wino ? 4 : 3;
   A2M_CHECK_ARG(fits32(xs_b) && fits32(xs_c) && fits32((int64_t)B * xs_b) && fits32((int64_t)B * ys_b) &&
@@ -816,36 +838,32 @@ static int wino_problem(WinoProblem& p, const float* x, int64_t xs_g, int64_t xs
   A2M_CHECK_ARG((reinterpret_cast<uintptr_t>(x) % 16) == 0 && xs_b % 4 == 0 && xs_c % 4 == 0 && xs_g % 4 == 0 &&
                     w_gs % 4 == 0 && (reinterpret_cast<uintptr_t>(packed) % 16) == 0,
                 "conv1d_wino: x rows / packed weights must be 16-byte aligned");
+  p.N = B * T; p.K = 3 * Ci;
   p.A = dense_rk(packed, Ci * kw, w_gs);
-  Gather Bg{};
-  Bg.base = x; Bg.bstride = xs_g;
-  Bg.sr0 = (int)xs_b; Bg.R1 = 1; Bg.R2 = T; Bg.sk0 = (int)xs_c;
-  Bg.K1 = Bg.K2 = 1; Bg.divh = Bg.divw = 1; Bg.Lh = Bg.Lw = 1;
-  Bg.cw = -1; Bg.tapconv = 3;
-  p.B = Bg;
-  Epilogue E = epi_bn(y, bias, bn_w, bn_b, bn_rm, bn_rv, bn_eps, act, slope);
-  E.N1 = 1; E.N2 = T; E.so0 = (int)ys_b; E.so1 = 0; E.so2 = (int)ys_t; E.som = (int)ys_c;
-  E.bstride = ys_g; E.pstride = Co;
-  E.res1 = res;
-  p.E = E;
+  p.B = tap_gather(x, xs_g, xs_b, xs_c, T, 3, -1);
+  p.E = conv1d_epi(E, T, ys_b, ys_c, ys_t);
+  p.E.bstride = ys_g; p.E.pstride = Co;
   return A2M_OK;
+}
+
+// the epilogue of a route query: no bias / BN / activation (a route does not depend on them)
+static Epilogue route_epi(float* y, const float* res = nullptr) {
+  Epilogue E = epi_bn(y, nullptr, nullptr, nullptr, nullptr, nullptr, 1e-5f, 0, 0.2f);
+  E.res1 = res;
+  return E;
 }
 
 int a2m_conv1d_wino_route(const float* x, int64_t xs_g, int64_t xs_b, int64_t xs_c, int32_t G, int32_t B,
                           int32_t Ci, int32_t T, const float* packed, int32_t Co, const float* res, float* y,
                           int64_t ys_g, int64_t ys_b, int64_t ys_c, int64_t ys_t, int32_t wino, int32_t out[8]) {
   A2M_CHECK_ARG(out != nullptr, "conv1d_wino_route: null out");
-  WinoProblem p;
-  const int rc = wino_problem(p, x, xs_g, xs_b, xs_c, G, B, Ci, T, packed, (int64_t)Co * Ci * 4, wino, nullptr, Co,
-                              nullptr, nullptr, nullptr, nullptr, 1e-5f, 0, 0.2f, res, y, ys_g, ys_b, ys_c, ys_t);
+  ConvProblem p;
+  const int rc = wino_problem(p, x, xs_g, xs_b, xs_c, G, B, Ci, T, packed, (int64_t)Co * Ci * 4, wino, Co,
+                              route_epi(y, res), ys_g, ys_b, ys_c, ys_t);
   if (rc != A2M_OK) return rc;
   RouteConfig cfg = route_config();
-  cfg.wino = wino;
-  const GemmRoute r = gemm_route(p.A, p.B, p.E, Co, B * T, 3 * Ci, G, 0, cfg);
-  const int32_t o[8] = {r.kind, r.tile, r.bk, r.splits, r.kchunk, r.ma, r.mb,
-                        (r.vec4 ? 1 : 0) | (r.mcontig ? 2 : 0) | (r.halo ? 4 : 0) | (r.reduce ? 8 : 0) |
-                            (r.wino ? 16 : 0)};
-  for (int i = 0; i < 8; ++i) out[i] = o[i];
+  cfg.xform = wino ? XFORM_WINO : XFORM_NONE;
+  route_out(gemm_route(p.A, p.B, p.E, Co, p.N, p.K, G, 0, cfg), out);
   return A2M_OK;
 }
 
@@ -855,17 +873,18 @@ int a2m_conv1d_wino_group_fwd_f32(const float* x, int64_t xs_g, int64_t xs_b, in
                                   const float* bn_rm, const float* bn_rv, float bn_eps, int32_t act,
                                   float slope, const float* res, float* y, int64_t ys_g, int64_t ys_b,
                                   int64_t ys_c, int64_t ys_t, void* ws, size_t ws_bytes, void* stream) {
-  WinoProblem p;
-  const int rc = wino_problem(p, x, xs_g, xs_b, xs_c, G, B, Ci, T, packed, w_gs, 1, bias, Co, bn_w, bn_b, bn_rm,
-                              bn_rv, bn_eps, act, slope, res, y, ys_g, ys_b, ys_c, ys_t);
+  ConvProblem p;
+  Epilogue E = epi_bn(y, bias, bn_w, bn_b, bn_rm, bn_rv, bn_eps, act, slope);
+  E.res1 = res;
+  const int rc = wino_problem(p, x, xs_g, xs_b, xs_c, G, B, Ci, T, packed, w_gs, 1, Co, E, ys_g, ys_b, ys_c, ys_t);
   if (rc != A2M_OK) return rc;
   RouteConfig cfg = route_config();
-  cfg.wino = 1;
-  A2M_CHECK_ARG(gemm_route(p.A, p.B, p.E, Co, B * T, 3 * Ci, G, 0, cfg).wino,
+  cfg.xform = XFORM_WINO;
+  A2M_CHECK_ARG(gemm_route(p.A, p.B, p.E, Co, p.N, p.K, G, 0, cfg).xform == XFORM_WINO,
                 "conv1d_wino: not a Winograd launch (fp32, T >= 16 with 64 %% T == 0, Ci %% 32 == 0, and a shape "
                 "the rule table keeps on it): B=%d Ci=%d Co=%d T=%d G=%d precision %d",
                 B, Ci, Co, T, G, cfg.prec);
-  return gemm(p.A, p.B, p.E, Co, B * T, 3 * Ci, G, ws, ws_bytes, as_stream(stream), 0, 1);
+  return gemm(p.A, p.B, p.E, Co, p.N, p.K, G, ws, ws_bytes, as_stream(stream), 0, XFORM_WINO);
 }
 
 int a2m_conv1d_wino_fwd_f32(const float* x, int64_t xs_b, int64_t xs_c, int32_t B, int32_t Ci, int32_t T,
@@ -877,31 +896,13 @@ int a2m_conv1d_wino_fwd_f32(const float* x, int64_t xs_b, int64_t xs_c, int32_t 
                                        bn_eps, act, slope, res, y, 0, ys_b, ys_c, ys_t, ws, ws_bytes, stream);
 }
 
-int a2m_conv1d_down_pack_f32(const float* w, int32_t Co, int32_t Ci, float* packed, void* stream) {
-  A2M_CHECK_ARG(w && packed && Co > 0 && Ci > 0 && Ci % 32 == 0, "conv1d_down_pack: bad args Co=%d Ci=%d (Ci %% 32)",
-                Co, Ci);
-  A2M_CHECK_ARG(fits32((int64_t)Co * Ci * 6), "conv1d_down_pack: too large");
-  hipLaunchKernelGGL(conv1d_down_pack_kernel, dim3((unsigned)std::min<int64_t>(cdiv((int64_t)Co * Ci, 256), 8192)),
-                     dim3(256), 0, as_stream(stream), w, Co, Ci, packed);
-  A2M_LAUNCH_CHECK();
-  return A2M_OK;
-}
-
-// the operands of a conv1d over t-contiguous x as the engine sees them: down = 1 A the weights
-// packed by a2m_conv1d_down_pack_f32 (6 Ci floats a row) and B the conv's plain gather of x; down
-// = 0 those of a2m_conv1d_fwd_f32 (`w` the plain weights; the im2col matrix stands in by its
-// alignment only: for route queries)
-struct DownProblem {
-  Gather A, B;
-  Epilogue E;
-  int N, K;
-};
-static int down_problem(DownProblem& p, const float* x, int64_t xs_b, int64_t xs_c, int32_t B, int32_t Ci,
-                        int32_t Tin, const float* w, int32_t down, const float* bias, int32_t Co, int32_t ks,
-                        int32_t stride, int32_t pad, const float* bn_w, const float* bn_b, const float* bn_rm,
-                        const float* bn_rv, float bn_eps, int32_t act, float slope, float* y, int64_t ys_b,
-                        int64_t ys_c, int64_t ys_t) {
-  A2M_CHECK_ARG(x && w && y, "conv1d_down: null pointer");
+// a2m_conv1d_down_*'s argument checks and the operands of the requested launch of a conv1d over
+// t-contiguous x: A the weights packed by a2m_conv1d_down_pack_f32 (6 Ci floats a row), B the
+// conv's plain gather of x, E (the caller's bias / BN / activation) addressed as the conv's output
+static int down_problem(ConvProblem& p, const float* x, int64_t xs_b, int64_t xs_c, int32_t B, int32_t Ci,
+                        int32_t Tin, const float* packed, int32_t Co, int32_t ks, int32_t stride, int32_t pad,
+                        const Epilogue& E, int64_t ys_b, int64_t ys_c, int64_t ys_t) {
+  A2M_CHECK_ARG(x && packed && E.out, "conv1d_down: null pointer");
   A2M_CHECK_ARG(B > 0 && Ci > 0 && Tin > 0 && Co > 0 && ks > 0 && stride > 0 && pad >= 0,
                 "conv1d_down: bad shape B=%d Ci=%d T=%d Co=%d k=%d s=%d p=%d", B, Ci, Tin, Co, ks, stride, pad);
   const int Tout = (Tin + 2 * pad - ks) / stride + 1;
@@ -909,27 +910,10 @@ static int down_problem(DownProblem& p, const float* x, int64_t xs_b, int64_t xs
   A2M_CHECK_ARG(fits32(xs_b) && fits32(xs_c) && fits32(ys_b) && fits32(ys_c) && fits32(ys_t) &&
                     fits32((int64_t)B * xs_b) && fits32((int64_t)B * ys_b) && fits32((int64_t)Co * Ci * 6),
                 "conv1d_down: tensor too large for 32-bit offsets");
-  const int64_t K = (int64_t)Ci * ks, N = (int64_t)B * Tout;
-  p.K = (int)K; p.N = (int)N;
-  p.A = dense_rk(w, down ? 6 * Ci : (int)K);
-  Gather Bg{};
-  if (!down && ks > 1 && ks <= 8 && stride <= 2 && Co >= 128 && K % 4 == 0 && N * K < (1LL << 31)) {
-    Bg = dense_rk(reinterpret_cast<const float*>(uintptr_t(256)), (int)K);   // the im2col matrix (workspace head)
-  } else if (!down && ks == 1 && pad == 0 && stride == 1 && xs_b == (int64_t)Tin) {
-    Bg = xs_c == 1 ? dense_rk(x, 1) : dense_kr(x, (int)xs_c);
-    if (xs_c != 1) Bg.sr0 = 1;
-  } else {
-    Bg.base = x; Bg.bstride = 0;
-    Bg.sr0 = (int)xs_b; Bg.R1 = 1; Bg.R2 = Tout; Bg.ar1 = 0; Bg.ar2 = stride;
-    Bg.sk0 = (int)xs_c; Bg.K1 = 1; Bg.K2 = ks; Bg.bk1 = 0; Bg.bk2 = 1;
-    Bg.ch = 0; Bg.cw = -pad; Bg.divh = Bg.divw = 1; Bg.Lh = 1; Bg.Lw = Tin;
-    Bg.sh = 0; Bg.sw = 1;
-    Bg.kcontig = (ks == 1 && xs_c == 1) ? 1 : 0;
-  }
-  p.B = Bg;
-  Epilogue E = epi_bn(y, bias, bn_w, bn_b, bn_rm, bn_rv, bn_eps, act, slope);
-  E.N1 = 1; E.N2 = Tout; E.so0 = (int)ys_b; E.so1 = 0; E.so2 = (int)ys_t; E.som = (int)ys_c;
-  p.E = E;
+  p.N = B * Tout; p.K = Ci * ks;
+  p.A = dense_rk(packed, 6 * Ci);
+  p.B = conv1d_gather(x, xs_b, xs_c, 1, Tin, Tout, ks, stride, pad);
+  p.E = conv1d_epi(E, Tout, ys_b, ys_c, ys_t);
   return A2M_OK;
 }
 
@@ -937,27 +921,21 @@ int a2m_conv1d_down_route(const float* x, int64_t xs_b, int64_t xs_c, int32_t B,
                           const float* w, int32_t Co, int32_t ks, int32_t stride, int32_t pad, float* y,
                           int64_t ys_b, int64_t ys_c, int64_t ys_t, int32_t down, int32_t out[8]) {
   A2M_CHECK_ARG(out != nullptr, "conv1d_down_route: null out");
+  ConvProblem p;
+  const int rc = down_problem(p, x, xs_b, xs_c, B, Ci, Tin, w, Co, ks, stride, pad, route_epi(y), ys_b, ys_c, ys_t);
+  if (rc != A2M_OK) return rc;
   RouteConfig cfg = route_config();
-  DownProblem p;
   GemmRoute r{};
   if (down) {
-    const int rc = down_problem(p, x, xs_b, xs_c, B, Ci, Tin, w, 1, nullptr, Co, ks, stride, pad, nullptr, nullptr,
-                                nullptr, nullptr, 1e-5f, 0, 0.2f, y, ys_b, ys_c, ys_t);
-    if (rc != A2M_OK) return rc;
-    cfg.down = 1;
+    cfg.xform = XFORM_DOWN;
     r = gemm_route(p.A, p.B, p.E, Co, p.N, p.K, 1, 0, cfg);
   }
-  if (!r.down) {   // no request, or refused: a2m_conv1d_fwd_f32's route with its operands
-    const int rc = down_problem(p, x, xs_b, xs_c, B, Ci, Tin, w, 0, nullptr, Co, ks, stride, pad, nullptr, nullptr,
-                                nullptr, nullptr, 1e-5f, 0, 0.2f, y, ys_b, ys_c, ys_t);
-    if (rc != A2M_OK) return rc;
-    cfg.down = 0;
+  if (r.xform != XFORM_DOWN) {   // no request, or refused: a2m_conv1d_fwd_f32's route with its operands
+    cfg.xform = XFORM_NONE;
+    p = conv1d_fwd_problem(x, xs_b, xs_c, 1, B, Ci, Tin, w, Co, ks, stride, pad, nullptr, p.E);
     r = gemm_route(p.A, p.B, p.E, Co, p.N, p.K, 1, 0, cfg);
   }
-  const int32_t o[8] = {r.kind, r.tile, r.bk, r.splits, r.kchunk, r.ma, r.mb,
-                        (r.vec4 ? 1 : 0) | (r.mcontig ? 2 : 0) | (r.halo ? 4 : 0) | (r.reduce ? 8 : 0) |
-                            (r.wino ? 16 : 0) | (r.down ? 32 : 0)};
-  for (int i = 0; i < 8; ++i) out[i] = o[i];
+  route_out(r, out);
   return A2M_OK;
 }
 
@@ -966,19 +944,19 @@ int a2m_conv1d_down_fwd_f32(const float* x, int64_t xs_b, int64_t xs_c, int32_t 
                             int32_t pad, const float* bn_w, const float* bn_b, const float* bn_rm,
                             const float* bn_rv, float bn_eps, int32_t act, float slope, float* y, int64_t ys_b,
                             int64_t ys_c, int64_t ys_t, void* ws, size_t ws_bytes, void* stream) {
-  DownProblem p;
-  const int rc = down_problem(p, x, xs_b, xs_c, B, Ci, Tin, packed, 1, bias, Co, ks, stride, pad, bn_w, bn_b, bn_rm,
-                              bn_rv, bn_eps, act, slope, y, ys_b, ys_c, ys_t);
+  ConvProblem p;
+  const int rc = down_problem(p, x, xs_b, xs_c, B, Ci, Tin, packed, Co, ks, stride, pad,
+                              epi_bn(y, bias, bn_w, bn_b, bn_rm, bn_rv, bn_eps, act, slope), ys_b, ys_c, ys_t);
   if (rc != A2M_OK) return rc;
   RouteConfig cfg = route_config();
-  cfg.down = 1;
+  cfg.xform = XFORM_DOWN;
   A2M_CHECK_ARG((reinterpret_cast<uintptr_t>(packed) % 16) == 0 &&
-                    gemm_route(p.A, p.B, p.E, Co, p.N, p.K, 1, 0, cfg).down,
+                    gemm_route(p.A, p.B, p.E, Co, p.N, p.K, 1, 0, cfg).xform == XFORM_DOWN,
                 "conv1d_down: not a down-sampling launch (fp32, k = 4, s = 2, p = 1, Tin >= 16 with 128 %% Tin == 0, "
                 "Ci %% 32 == 0, x rows 16-byte aligned, and a shape the rule table keeps on it): B=%d Ci=%d Co=%d "
                 "Tin=%d k=%d s=%d p=%d precision %d",
                 B, Ci, Co, Tin, ks, stride, pad, cfg.prec);
-  return gemm(p.A, p.B, p.E, Co, p.N, p.K, 1, ws, ws_bytes, as_stream(stream), 0, 0, 1);
+  return gemm(p.A, p.B, p.E, Co, p.N, p.K, 1, ws, ws_bytes, as_stream(stream), 0, XFORM_DOWN);
 }
 
 int a2m_convt1d_pack_f32(const float* w, int32_t Ci, int32_t Co, int32_t ks, int32_t stride,
@@ -1046,8 +1024,7 @@ int a2m_convt1d_tap_fwd_f32(const float* x, int64_t xs_b, int64_t xs_c, int32_t 
     int kk0 = -1, ntap = 0;
     for (int kk = 0; kk < ks; ++kk)
       if ((((r + pad - kk) % stride) + stride) % stride == 0) { if (kk0 < 0) kk0 = kk; ++ntap; }
-    p.E = epi_bn(y + r, bias, bn_w, bn_b, bn_rm, bn_rv, bn_eps, act, slope);
-    p.E.N1 = 1; p.E.N2 = Tin; p.E.so0 = (int)ys_b; p.E.so1 = 0; p.E.so2 = stride; p.E.som = (int)ys_c;
+    p.E = conv1d_epi(epi_bn(y + r, bias, bn_w, bn_b, bn_rm, bn_rv, bn_eps, act, slope), Tin, ys_b, ys_c, stride);
     p.K = ntap * Ci;
     p.A = dense_rk(ntap ? packed + off : packed, ntap ? ntap * Ci : 1);
     p.B = dense_rk(x, 1);
@@ -1055,12 +1032,7 @@ int a2m_convt1d_tap_fwd_f32(const float* x, int64_t xs_b, int64_t xs_c, int32_t 
     const int cw = (r + pad - kk0) / stride - ntap + 1;
     A2M_CHECK_ARG(cw > -Tin && cw + ntap - 1 < Tin, "convt1d_tap: tap shift %d..%d outside the clip",
                   cw, cw + ntap - 1);
-    Gather Bg{};
-    Bg.base = x; Bg.bstride = 0;
-    Bg.sr0 = (int)xs_b; Bg.R1 = 1; Bg.R2 = Tin; Bg.sk0 = (int)xs_c;
-    Bg.K1 = Bg.K2 = 1; Bg.divh = Bg.divw = 1; Bg.Lh = Bg.Lw = 1;
-    Bg.cw = cw; Bg.tapconv = ntap;
-    p.B = Bg;
+    p.B = tap_gather(x, 0, xs_b, xs_c, Tin, ntap, cw);
     off += (size_t)Co * ntap * Ci;
     return A2M_OK;
   };

@@ -282,10 +282,7 @@ int a2m_gemm_f32_route(int32_t M, int32_t N, int32_t N1, int32_t K, int32_t K1, 
   const int rc = gemm_f32_problem(p, M, N, N1, K, K1, batch, A, a_bs, a_m, a_k0, a_k1, B, b_bs, b_n0, b_n1, b_k0,
                                   b_k1, C, c_bs, c_m, c_n0, c_n1, bias, alpha, accumulate);
   if (rc != A2M_OK) return rc;
-  const a2m::GemmRoute r = a2m::gemm_route(p.A, p.B, p.E, M, N, K, batch, 0, a2m::route_config());
-  const int32_t o[8] = {r.kind, r.tile, r.bk, r.splits, r.kchunk, r.ma, r.mb,
-                        (r.vec4 ? 1 : 0) | (r.mcontig ? 2 : 0) | (r.halo ? 4 : 0) | (r.reduce ? 8 : 0)};
-  for (int i = 0; i < 8; ++i) out[i] = o[i];
+  a2m::route_out(a2m::gemm_route(p.A, p.B, p.E, M, N, K, batch, 0, a2m::route_config()), out);
   return A2M_OK;
 }
 

@@ -16,6 +16,7 @@ import pytest
 import torch
 
 from conftest import rel_err
+from conv_helpers import bn_lrelu_ref, bn_params as _bn, plan_override  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 DEV = 'cuda'
@@ -34,21 +35,6 @@ def _inputs(B, Ci, Co, T, seed=0):
     w = torch.randn(Co, Ci, 4, generator=g) / np.sqrt(4 * Ci)
     b = torch.randn(Co, generator=g)
     return x, w, b
-
-
-def _bn(Co, g):
-    return tuple(t.to(DEV) for t in (torch.rand(Co, generator=g) + 0.5, torch.randn(Co, generator=g),
-                                     torch.randn(Co, generator=g) * 0.1, torch.rand(Co, generator=g) + 0.5)) + (1e-5,)
-
-
-@pytest.fixture
-def plan_override():
-    from a2m import _native as N
-
-    def set_plan(tile, splits):
-        N.check(N.lib.a2m_gemm_plan_override(tile, splits))
-    yield set_plan
-    N.check(N.lib.a2m_gemm_plan_override(0, 0))
 
 
 @pytest.mark.parametrize('B,Ci,Co,T', SHAPES)
@@ -98,10 +84,7 @@ def test_down_conv1d_epilogue_views_and_cache():
     bn = _bn(Co, g)
 
     def ref_of(w):
-        z = _conv_ref(x.cpu(), w.cpu(), bias.cpu())
-        wq, bq, rm, rv, eps = (t.cpu().double() if torch.is_tensor(t) else t for t in bn)
-        z = (z - rm.view(1, -1, 1)) / torch.sqrt(rv.view(1, -1, 1) + eps) * wq.view(1, -1, 1) + bq.view(1, -1, 1)
-        return torch.where(z > 0, z, 0.2 * z)
+        return bn_lrelu_ref(_conv_ref(x.cpu(), w.cpu(), bias.cpu()), bn)
 
     cache = {}
     y = F.conv1d(x, w, bias, 2, 1, bn=bn, act=F.ACT_LRELU, slope=0.2, cache=cache, wino=True)

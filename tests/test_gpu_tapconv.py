@@ -13,6 +13,7 @@ import pytest
 import torch
 
 from conftest import golden, rel_err
+from conv_helpers import bn_params
 
 pytestmark = pytest.mark.gpu
 DEV = 'cuda'
@@ -67,10 +68,7 @@ def _tap_cases():
         b = torch.randn(Co, generator=g).to(DEV)
         kw = {}
         if i == len(_HALO_CASES) - 1:
-            kw = dict(bn=tuple(t.to(DEV) for t in (torch.rand(Co, generator=g) + 0.5, torch.randn(Co, generator=g),
-                                                   torch.randn(Co, generator=g) * 0.1,
-                                                   torch.rand(Co, generator=g) + 0.5)) + (1e-5,),
-                      act=F.ACT_LRELU, slope=0.2)
+            kw = dict(bn=bn_params(Co, g), act=F.ACT_LRELU, slope=0.2)
         cache = {}
         outs.append(F.conv1d(x, w, b, 1, 1, cache=cache, **kw).cpu())
         assert 'w' in cache, 'tap path not taken'
@@ -255,8 +253,7 @@ def test_conv2d_nhwc_interp_equals_conv_then_interp(B, T, split):
     x = torch.randn(B, H, 16, 512, generator=g).to(DEV)   # conv3's NHWC output [B, H, 16, 512]
     w = (torch.randn(256, 512, 3, 8, generator=g) / np.sqrt(512 * 24)).to(DEV)
     b = torch.randn(256, generator=g).to(DEV)
-    bn = tuple(t.to(DEV) for t in (torch.rand(256, generator=g) + 0.5, torch.randn(256, generator=g),
-                                     torch.randn(256, generator=g) * 0.1, torch.rand(256, generator=g) + 0.5)) + (1e-5,)
+    bn = bn_params(256, g)
     cache = {}
     N.check(N.lib.a2m_gemm_plan_override(64 if split else 0, split))
     try:

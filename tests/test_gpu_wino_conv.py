@@ -13,6 +13,7 @@ import pytest
 import torch
 
 from conftest import rel_err
+from conv_helpers import bn_lrelu_ref, bn_params as _bn, plan_override  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 DEV = 'cuda'
@@ -31,21 +32,6 @@ def _inputs(B, Ci, Co, T, seed=0):
     w = torch.randn(Co, Ci, 3, generator=g) / np.sqrt(3 * Ci)
     b = torch.randn(Co, generator=g)
     return x, w, b
-
-
-def _bn(Co, g):
-    return tuple(t.to(DEV) for t in (torch.rand(Co, generator=g) + 0.5, torch.randn(Co, generator=g),
-                                     torch.randn(Co, generator=g) * 0.1, torch.rand(Co, generator=g) + 0.5)) + (1e-5,)
-
-
-@pytest.fixture
-def plan_override():
-    from a2m import _native as N
-
-    def set_plan(tile, splits):
-        N.check(N.lib.a2m_gemm_plan_override(tile, splits))
-    yield set_plan
-    N.check(N.lib.a2m_gemm_plan_override(0, 0))
 
 
 @pytest.mark.parametrize('B,Ci,Co,T', SHAPES)
@@ -95,10 +81,7 @@ def test_wino_conv1d_epilogue_views_residual_and_cache():
     bn = _bn(Co, g)
 
     def ref_of(w):
-        z = _conv_ref(x.cpu(), w.cpu(), bias.cpu())
-        wq, bq, rm, rv, eps = (t.cpu().double() if torch.is_tensor(t) else t for t in bn)
-        z = (z - rm.view(1, -1, 1)) / torch.sqrt(rv.view(1, -1, 1) + eps) * wq.view(1, -1, 1) + bq.view(1, -1, 1)
-        return torch.where(z > 0, z, 0.2 * z)
+        return bn_lrelu_ref(_conv_ref(x.cpu(), w.cpu(), bias.cpu()), bn)
 
     outbuf = torch.zeros(B, T, 2 * Co, device=DEV)
     out = outbuf[:, :, Co:].permute(0, 2, 1)
