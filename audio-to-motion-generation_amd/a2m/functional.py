@@ -1143,6 +1143,50 @@ def diff_time_bwd(dy, dx=None, accumulate=False):
     return dx
 
 
+def _check_f64(t, shape, name):
+    if not t.is_cuda:
+        raise RuntimeError('a2m ops need device tensors (no CPU fallback); got a CPU tensor')
+    if t.dtype != torch.float64:
+        raise TypeError(f'{name} accumulates in float64; got {t.dtype}')
+    assert t.is_contiguous() and tuple(t.shape) == shape, (name, tuple(t.shape), shape)
+
+
+def val_motion(fake_pose, real_pose, motion=None, part=None):
+    """The first launch of the validation pass (a2m_val_motion_f32): motion [2B, T-1, Fd] =
+    diff_t of fake_pose (rows 0..B-1) and of real_pose (rows B..2B-1), ready for one stacked
+    discriminator forward, and part [B, 3] float64, each clip's sums of |motion difference|, of
+    the acceleration norms and of the jerk norms.  Returns (motion, part); both may be passed in
+    to be reused."""
+    _check_dev(fake_pose, real_pose, motion)
+    assert fake_pose.dim() == 3 and fake_pose.shape == real_pose.shape
+    fake_pose, real_pose = fake_pose.contiguous(), real_pose.contiguous()
+    B, T, Fd = fake_pose.shape
+    if motion is None:
+        motion = torch.empty(2 * B, T - 1, Fd, device=fake_pose.device)
+    if part is None:
+        part = torch.empty(B, 3, dtype=torch.float64, device=fake_pose.device)
+    assert motion.is_contiguous() and tuple(motion.shape) == (2 * B, T - 1, Fd)
+    _check_f64(part, (B, 3), 'part')
+    N.check(N.lib.a2m_val_motion_f32(_p(fake_pose), _p(real_pose), B, T, Fd, _p(motion), _p(part), _stream()))
+    return motion, part
+
+
+def val_finish(part, T, Fd, logits, bone, angle, lambda_gan, lambda_d, acc):
+    """The second launch (a2m_val_finish_f32): adds [g_loss, d_loss, bone, angle, smoothness, jerk,
+    motion_l1, 1] of one dev batch to acc (float64 [8]) from val_motion's part [B, 3], the
+    discriminator's logits [2B, L] on val_motion's motion (fake rows first) and the generator's
+    bone / angle device scalars.  Returns acc."""
+    _check_dev(logits, bone, angle)
+    B = part.shape[0]
+    _check_f64(part, (B, 3), 'part')
+    _check_f64(acc, (8,), 'acc')
+    logits = logits.contiguous()
+    assert logits.dim() == 2 and logits.shape[0] == 2 * B and bone.numel() == 1 and angle.numel() == 1
+    N.check(N.lib.a2m_val_finish_f32(_p(part), B, T, Fd, _p(logits), logits.shape[1], _p(bone), _p(angle),
+                                     float(lambda_gan), float(lambda_d), _p(acc), _stream()))
+    return acc
+
+
 def gather_segments_(dst, segments):
     """dst[off:off + t.numel()] = t.reshape(-1) for every (off, t) in segments (contiguous fp32
     device tensors), 48 segments per launch (a2m_gather_segments_f32)."""

@@ -5,6 +5,8 @@ over clips with one process per GPU.
                        learning-rate adaptation, smoothed noisy labels)
   pos_to_motion        :208-213        compute_temporal_smoothness_loss :216-230
   compute_jerk_loss    :233-248        one iteration (G steps, then D steps) :342-414
+  validation pass      :427-499 (GANTrainer.validate)
+  epoch loop, checkpoints, loss record  :325-329, 501-532 (GANTrainer.fit)
 
 Data parallelism: every rank runs the step on its shard of the batch.
 Gradients of the network being stepped are averaged by GradReducer: the optimiser's flat
@@ -21,6 +23,7 @@ are frozen during the G steps: the reference computes their gradients there and 
 away (optimizer_D.zero_grad() at :388).
 """
 import contextlib
+import os
 import time
 
 import numpy as np
@@ -386,6 +389,7 @@ class GANTrainer:
         self._captured = {'g': None, 'd': None}
         self._warm = {'g': 0, 'd': 0}
         self._seed_ctr = None
+        self._val_bufs = {}                       # validate(): per batch shape (motion, part)
         if self.graphs:
             dev = next(generator.parameters()).device
             if dev.type != 'cuda':
@@ -578,3 +582,148 @@ class GANTrainer:
             d_val, g_val = pair.tolist()
             self.dyn.update_loss_history(d_val, g_val)
         return d_loss, g_loss
+
+    # ---------------------------------------------------------------- validation epoch
+    VAL_KEYS = ('g_loss', 'd_loss', 'bone_loss', 'angle_loss', 'smoothness_loss', 'jerk_loss', 'motion_l1')
+
+    def _val_buffers(self, B, T, Fd, dev):
+        """The stacked motion [2B, T-1, Fd] and the per-clip partials [B, 3] of one batch shape,
+        kept between batches and epochs (one stream: a batch's launches finish with them before
+        the next batch's start)."""
+        cache, key = self._val_bufs, (B, T, Fd, str(dev))
+        if key not in cache:
+            cache[key] = (torch.empty(2 * B, T - 1, Fd, device=dev),
+                          torch.empty(B, 3, dtype=torch.float64, device=dev))
+        return cache[key]
+
+    def _validate_accumulate(self, batches):
+        """The device side of validate(): per batch one eval G forward, val_motion, one eval D
+        forward on the stacked fake / real motion and val_finish, all queued on the caller's
+        stream with no host synchronisation.  Returns (acc, n): the float64 [8] sums on the device
+        and the number of batches this rank queued."""
+        dev = next(self.G.parameters()).device
+        acc = torch.zeros(8, dtype=torch.float64, device=dev)
+        flags = [(m, m.training) for net in (self.G, self.D) for m in net.modules()]
+        n = 0
+        try:
+            self.G.eval()
+            self.D.eval()
+            with torch.no_grad():
+                for audio, real_pose in batches:
+                    audio = audio.to(dev, torch.float32)
+                    real_pose = real_pose.to(dev, torch.float32)
+                    fake_pose, internal = self.G(audio, real_pose=real_pose)
+                    zero = None
+                    if len(internal) < 2:  # the reference's defaults (:447-448)
+                        zero = torch.zeros((), device=dev)
+                    bone = internal[0] if len(internal) > 0 else zero
+                    angle = internal[1] if len(internal) > 1 else zero
+                    B, T, Fd = fake_pose.shape
+                    motion, part = F.val_motion(fake_pose, real_pose, *self._val_buffers(B, T, Fd, dev))
+                    logits, _ = self.D(motion)
+                    F.val_finish(part, T, Fd, logits.reshape(2 * B, -1), bone, angle, self.lambda_gan,
+                                 self.lambda_d, acc)
+                    n += 1
+        finally:
+            for m, flag in flags:
+                m.training = flag
+        return acc, n
+
+    def _validate_read(self, acc):
+        """The pass's one device-to-host read: 8 doubles."""
+        return acc.tolist()
+
+    def validate(self, batches):
+        """The validation pass of version5_model_train.py:427-499 over `batches`, an iterable of
+        (audio [B, T, 128], real_pose [B, T, 104]) with the poses normalised as the reference's
+        norm_pose_list_dev, on the host or the device, of any batch sizes.  Returns the reference's
+        averages as Python floats, every batch weighing the same: g_loss, d_loss, bone_loss,
+        angle_loss, smoothness_loss, jerk_loss, motion_l1, and steps, the number of batches.
+
+        Per batch: G's eval forward with the real pose, val_motion, ONE D eval forward on the
+        stacked [2B, T-1, 104] motion (in eval mode D treats every clip on its own -- BatchNorm
+        reads running statistics, attention and the graphs are per clip -- so the stacked forward
+        is the reference's separate forwards; its third D call repeats its first and is not run),
+        val_finish.  The labels are ones and zeros (:463-464).  The sums stay on the device in
+        float64; the host reads 8 doubles once, after the last batch.
+
+        Runs under no_grad in eval mode and puts every submodule's training flag back, also when
+        a batch raises; touches no gradient, optimiser, label generator, dropout seed counter or
+        schedule state, and is never captured in a graph (it runs eagerly on the caller's stream
+        also with graphs=True).  Data-parallel: the sums are all-reduced before the division, so
+        every rank returns the average over the union of all ranks' batches; ranks may hold
+        different numbers of batches, but every rank must call.  No batch at all (over all ranks)
+        raises ValueError('no batches')."""
+        acc, _ = self._validate_accumulate(batches)
+        if self._collectives:
+            dist.all_reduce(acc, op=dist.ReduceOp.SUM, group=self.pg)
+        sums = self._validate_read(acc)
+        steps = int(round(sums[7]))
+        if steps == 0:
+            raise ValueError('no batches')
+        out = {k: v / steps for k, v in zip(self.VAL_KEYS, sums)}
+        out['steps'] = steps
+        return out
+
+    def fit(self, train_batches, dev_batches, n_epochs, save_dir=None, log_every=200, log=print,
+            start_epoch=0):
+        """The epoch loop of version5_model_train.py:325-532: n_epochs epochs numbered from
+        start_epoch.  train_batches and dev_batches are iterated once per epoch (lists or loaders
+        of (audio, real_pose), host or device tensors).
+
+        Per epoch: the schedule's frequency and learning-rate adjustments, iteration() per train
+        batch, validate(dev_batches), and with save_dir set the reference's files, written by rank
+        0 after flush(): gen/Best_Gen when this epoch's validation G loss is strictly below every
+        earlier one of this call (:508), gen/epoch_<n>, dis/epoch_<n> and loss.npy, each torch.save
+        of a state_dict (of the loss record for loss.npy), as the reference's loader and
+        a2m.inference.load_generator read them.  Every log_every-th batch (i % log_every ==
+        log_every - 1) the batch's D and G losses -- the values iteration() has already read for
+        the schedule, averaged over the ranks -- are logged through `log` and appended to train_d /
+        train_g.
+
+        Returns the loss record: train_g, train_d, val_g, val_d, val_terms (validate()'s dict per
+        epoch) and dynamic_stats with g_lr_history, d_lr_history, g_freq_history, d_freq_history,
+        one entry per epoch (the reference keeps only the last; these end with it)."""
+        stats = dict(g_lr_history=[], d_lr_history=[], g_freq_history=[], d_freq_history=[])
+        rec = dict(train_g=[], train_d=[], val_g=[], val_d=[], val_terms=[], dynamic_stats=stats)
+        dev = next(self.G.parameters()).device
+        last = start_epoch + n_epochs
+        for epoch in range(start_epoch, last):
+            g_freq, d_freq = self.dyn.adjust_training_frequency(epoch)
+            self.dyn.adjust_learning_rates(self.opt_G, self.opt_D, epoch)
+            for i, (audio, real_pose) in enumerate(train_batches):
+                self.iteration(audio.to(dev, torch.float32), real_pose.to(dev, torch.float32), epoch=epoch,
+                               g_freq=g_freq, d_freq=d_freq)
+                if i % log_every == log_every - 1:
+                    d_val, g_val = self.dyn.d_loss_history[-1], self.dyn.g_loss_history[-1]
+                    recent_d, recent_g = self.dyn.get_recent_avg_loss()
+                    log(f'[Epoch {epoch}/{last}] [Batch {i + 1}] [D loss: {d_val:f}] [G loss: {g_val:f}] '
+                        f'[Recent D: {recent_d:f}] [Recent G: {recent_g:f}] [G_freq: {g_freq}] [D_freq: {d_freq}]')
+                    rec['train_g'].append(g_val)
+                    rec['train_d'].append(d_val)
+            val = self.validate(dev_batches)
+            rec['val_g'].append(val['g_loss'])
+            rec['val_d'].append(val['d_loss'])
+            rec['val_terms'].append(val)
+            log(f"[Validation] Epoch {epoch}/{last} | G_loss: {val['g_loss']:.4f} | D_loss: {val['d_loss']:.4f}")
+            log(f"  Bone Loss: {val['bone_loss']:.4f} | Angle Loss: {val['angle_loss']:.4f} | "
+                f"Smoothness Loss: {val['smoothness_loss']:.4f} | Jerk Loss: {val['jerk_loss']:.4f}")
+            stats['g_lr_history'].append(self.dyn.g_lr_current)
+            stats['d_lr_history'].append(self.dyn.d_lr_current)
+            stats['g_freq_history'].append(g_freq)
+            stats['d_freq_history'].append(d_freq)
+            if save_dir is None:
+                continue
+            self.flush()
+            if self.rank != 0:
+                continue
+            gen_dir, dis_dir = os.path.join(save_dir, 'gen'), os.path.join(save_dir, 'dis')
+            os.makedirs(gen_dir, exist_ok=True)
+            os.makedirs(dis_dir, exist_ok=True)
+            if val['g_loss'] < min(rec['val_g'][:-1], default=float('inf')):
+                log(f'New best G model at epoch {epoch}, saving...')
+                torch.save(self.G.state_dict(), os.path.join(gen_dir, 'Best_Gen'))
+            torch.save(self.G.state_dict(), os.path.join(gen_dir, f'epoch_{epoch}'))
+            torch.save(self.D.state_dict(), os.path.join(dis_dir, f'epoch_{epoch}'))
+            torch.save(rec, os.path.join(save_dir, 'loss.npy'))
+        return rec

@@ -660,6 +660,30 @@ int a2m_diff_time_f32(const float* x, int32_t B, int32_t T, int32_t Fd, float* y
 int a2m_diff_time_bwd_f32(const float* dy, int32_t B, int32_t T, int32_t Fd, float* dx,
                           int32_t accumulate, void* stream);
 
+/* The validation pass of one dev batch (version5_model_train.py:438-480) in two launches around a
+ * single discriminator forward.
+ * a2m_val_motion_f32: fake_pose, real_pose [B][T][Fd] contiguous.  motion [2B][T-1][Fd]: rows
+ * 0..B-1 = diff_t(fake_pose), rows B..2B-1 = diff_t(real_pose), each the one float32 subtraction
+ * of a2m_diff_time_f32.  part [B][3] (float64, the caller's own buffer, not the workspace: D's
+ * GEMMs use that between the two launches): per clip the sums of |diff(real) - diff(fake)|, of
+ * the acceleration norms over t < T-2 and of the jerk norms over t < T-3, the norms in float32 as
+ * a2m_motion_losses_f32 takes them, the sums in float64.  One workgroup per clip; every pose
+ * element is loaded once.  T >= 2 (no upper bound), Fd <= 1920, T * Fd < 2^31.
+ * a2m_val_finish_f32: logits [2B][L] = D's output on `motion` (fake rows first); bone, angle:
+ * device scalars (the generator's internal losses).  One workgroup adds to acc [8] (float64,
+ * never overwritten: zero it once per epoch)
+ *   motion_l1 + lambda_gan * mean((fake_logits - 1)^2),
+ *   mean((real_logits - 1)^2) + lambda_d * mean(fake_logits^2),
+ *   bone, angle, smoothness, jerk, motion_l1, 1
+ * with motion_l1 = sum / (B (T-1) Fd), smoothness = sum / (B (T-2)), jerk = sum / (B (T-3)); a
+ * term over no frames is 0 (smoothness at T = 2, jerk at T <= 3).  All sums run in float64 in a
+ * fixed order, with no atomics: the same inputs give the same bits on every run. */
+int a2m_val_motion_f32(const float* fake_pose, const float* real_pose, int32_t B, int32_t T, int32_t Fd,
+                       float* motion, double* part, void* stream);
+int a2m_val_finish_f32(const double* part, int32_t B, int32_t T, int32_t Fd, const float* logits,
+                       int32_t L, const float* bone, const float* angle, float lambda_gan,
+                       float lambda_d, double* acc, void* stream);
+
 /* General strided GEMM on the same MFMA engine (linear layers' backward, 1x1 projections):
  *   C[m][n] (+)= alpha * sum_k A(m,k) B(n,k) (+ bias[m]), per batch z < batch
  *   n = n0*N1 + n1, k = k0*K1 + k1 (two-level index spaces cover [B][C][T] row sets)
