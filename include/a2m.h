@@ -768,6 +768,35 @@ int a2m_window_gather_f32(const float* data, int64_t length, int32_t C, const in
                           int32_t n_windows, int32_t window, int32_t interval, const float* mean,
                           const float* std_, float* out, void* stream);
 
+/* One batch of the HBM-resident PATS loader (a2m.data.PatsLoader; dataUtils.py:638-665 and :745-758
+ * for every clip of a DataLoader batch, and version5_model_train.py:296-319 for the poses) in one
+ * launch.  For modality m < n_mod (1..A2M_BATCH_MAX_MOD), clip b < n and j < ceil(window[m] /
+ * interval[m]):
+ *   sample = order[b0 + b]
+ *   out[m][b][j][:] = f(arena[m][start[m][sample] + j*interval[m]][:])
+ * arena[m]: [rows][C[m]] float32, every interval of every split concatenated; start[m]: int64, the
+ * arena row of each sample's window start; order: int64, the epoch's permutation.  order and
+ * start are device arrays read by the kernel, so the launch has no host synchronisation, captures
+ * into a HIP graph, and a replay after order was overwritten gathers the new clips.  The arrays
+ * arena .. out are host arrays of n_mod entries, read during the call.
+ * mode[m]: A2M_BATCH_RAW copies bitwise (mean[m] and std_[m] must be NULL); A2M_BATCH_STANDARDISE
+ * is a2m_window_gather_f32's (x - mean[c]) / (std[c] < 1e-7 ? 1 : std[c]); A2M_BATCH_NECKSUB
+ * (C[m] == 104 only) is a2m_pose_normalize_f32's ((x - neck) - mean[c]) / std[c], neck = column 0
+ * for c < 52, else column 52.  Both need mean[m] and std_[m] ([C[m]] device floats).
+ * C[m] % 4 == 0 and arena[m], out[m] 16-byte aligned: the kernel moves float4.  The kernel checks
+ * no bounds: the caller guarantees order[b0 .. b0+n) valid samples and start + window within the
+ * arena.  A2M_EINVAL before any launch for n_mod out of range, n < 0 or b0 < 0, and with n > 0 for a
+ * NULL array, arena, start, out or order, window or interval <= 0, an unknown mode, or mean / std
+ * not as the mode requires.  n = 0 returns A2M_OK without a launch and accepts NULL pointers. */
+#define A2M_BATCH_MAX_MOD 4
+#define A2M_BATCH_RAW 0
+#define A2M_BATCH_STANDARDISE 1
+#define A2M_BATCH_NECKSUB 2
+int a2m_batch_gather_f32(int32_t n_mod, const float* const* arena, const int64_t* const* start,
+                         const int32_t* C, const int32_t* window, const int32_t* interval,
+                         const int32_t* mode, const float* const* mean, const float* const* std_,
+                         float* const* out, const int64_t* order, int64_t b0, int32_t n, void* stream);
+
 /* ---- Pose video and track stitching ----
  * a2m_render_poses_u8 stands in for the drawing of generate_motion_video.py:66-164
  * (plot_head/body/hand_keypoints, draw_pose, draw_side_by_side_poses): every frame's P poses, each
