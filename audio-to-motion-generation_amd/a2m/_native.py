@@ -151,6 +151,9 @@ SIGNATURES = {
     'a2m_diff_time_bwd_f32': (ctypes.c_int, [P, I32, I32, I32, P, I32, P]),
     'a2m_val_motion_f32': (ctypes.c_int, [P, P, I32, I32, I32, P, P, P]),
     'a2m_val_finish_f32': (ctypes.c_int, [P, I32, I32, I32, P, I32, P, P, F32, F32, P, P]),
+    'a2m_eval_clip_f32': (ctypes.c_int, [P, P, P, P, P, I32, I32, I32, I32, F64, I32, F64, F64, P, P, P, P, P]),
+    'a2m_eval_gram_f64': (ctypes.c_int, [P, P, P, I32, I32, I32, I32, P, P, P]),
+    'a2m_eval_finish_f64': (ctypes.c_int, [P, P, P, I32, I32, I32, P, P, P]),
     'a2m_adam_f32': (ctypes.c_int, [P, P, P, P, I64, F32, F32, F32, F32, F32, I32, P]),
     'a2m_adam_dev_f32': (ctypes.c_int, [P, P, P, P, I64, P, F32, F32, F32, F32, P, P]),
     'a2m_gather_segments_f32': (ctypes.c_int, [P, P, P, I32, P, P]),

@@ -256,7 +256,7 @@ class PatsLoader:
             host = np.concatenate(parts) if parts else np.zeros((0, C), np.float32)
             self.arena[mod] = torch.from_numpy(host).to(self.device)
             self.channels[mod] = C
-        self._buffers = {}
+        self._buffers, self._style_buffers = {}, {}
         self._upload_tables()
         for s in SPLITS:
             setattr(self, s, _DictView(self, s))
@@ -295,6 +295,9 @@ class PatsLoader:
         for s in SPLITS:
             style += [np.full(n, ix.style[iid], np.float32) for iid, n in zip(ix.intervals[s], ix.sizes[s])]
         self._style = torch.from_numpy(np.concatenate(style) if style else np.zeros(0, np.float32)).to(self.device)
+        # the same ids as integers, for pairs(with_style=True); _style stays what .train / .dev / .test yield
+        self._style_i32 = torch.from_numpy(np.concatenate(style).astype(np.int32) if style
+                                           else np.zeros(0, np.int32)).to(self.device)
         self._meta = {}
         self.dropped = {s: dp_plan(ix.size(s), self.batch_size, self.rank, self.world)[1] for s in SPLITS}
         self._buffers.clear()
@@ -364,14 +367,16 @@ class PatsLoader:
         return None if t is None else torch.as_tensor(t).to(self.device, torch.float32).contiguous()
 
     def pairs(self, split, pose_mean=None, pose_std=None, audio_mean=None, audio_std=None, copy=False,
-              order=None):
+              order=None, with_style=False):
         """A re-iterable of (audio [n, T, 128], real_pose [n, T, 104]) for GANTrainer.fit /
         validate, one launch a batch.  With pose statistics the poses are neck-subtracted and
         normalised as necksub_normalize, with audio statistics the audio is standardised as
         gather_windows; without, raw.  The output buffers are reused per batch size: a yielded
         batch is valid until the next one is asked for (the trainer consumes a batch before the
         next is formed, on one stream); copy=True yields fresh tensors for callers that keep
-        batches.  order: the caller's order of the split's global indices instead of a drawn one."""
+        batches.  order: the caller's order of the split's global indices instead of a drawn one.
+        with_style=True yields (audio, real_pose, style), style the int32 [n] speaker ids of the
+        batch's clips, looked up on the device (one more launch a batch, no synchronisation)."""
         if (pose_mean is None) != (pose_std is None) or (audio_mean is None) != (audio_std is None):
             raise ValueError('mean and std come together')
         if order is not None:
@@ -382,7 +387,7 @@ class PatsLoader:
                   self._stat(audio_std)),
                  (pose, MODE_RAW if pose_mean is None else MODE_NECKSUB, self._stat(pose_mean),
                   self._stat(pose_std))]
-        return _Pairs(self, split, specs, copy, order)
+        return _Pairs(self, split, specs, copy, order, with_style)
 
 
 class _View:
@@ -404,9 +409,9 @@ class _View:
 
 
 class _Pairs(_View):
-    def __init__(self, loader, split, specs, copy, order):
+    def __init__(self, loader, split, specs, copy, order, with_style=False):
         super().__init__(loader, split, order)
-        self.specs, self.copy = specs, copy
+        self.specs, self.copy, self.with_style = specs, copy, with_style
 
     def _run(self, host, order_dev, plan):
         ld = self.loader
@@ -415,7 +420,16 @@ class _Pairs(_View):
             outs = ld.gather(order_dev, b0, n, self.specs, outs)
             if not self.copy:
                 ld._buffers[n] = outs
-            yield tuple(outs)
+            if not self.with_style:
+                yield tuple(outs)
+                continue
+            style = None if self.copy else ld._style_buffers.get(n)
+            if style is None:
+                style = torch.empty(n, dtype=torch.int32, device=ld.device)
+                if not self.copy:
+                    ld._style_buffers[n] = style
+            torch.index_select(ld._style_i32, 0, order_dev[b0:b0 + n], out=style)
+            yield (*outs, style)
 
 
 class _DictView(_View):

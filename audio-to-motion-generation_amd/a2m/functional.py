@@ -1187,6 +1187,81 @@ def val_finish(part, T, Fd, logits, bone, angle, lambda_gan, lambda_d, acc):
     return acc
 
 
+def _check_int(t, dtype, shape, name):
+    if not t.is_cuda:
+        raise RuntimeError('a2m ops need device tensors (no CPU fallback); got a CPU tensor')
+    if t.dtype != dtype:
+        raise TypeError(f'{name} must be {dtype}; got {t.dtype}')
+    assert t.is_contiguous() and tuple(t.shape) == shape, (name, tuple(t.shape), shape)
+
+
+def eval_clip(fake_norm, real_px, style, mean, std, n_styles, alpha, speed_width, accel_width, hist,
+              fake_px=None, part=None, hits=None):
+    """The first launch of the evaluation pass (a2m_eval_clip_f32): fake_px = fake_norm * std + mean
+    [B, T, F], and per clip the PCK hits [B] (int32) and part [B, 3] (float64: the sums of
+    |fake_px - real_px|, of the real and of the generated speeds); every speed and acceleration of
+    both poses is counted in hist [n_styles, 4, n_bins] (int64, added to).  A clip whose style
+    (int32 [B]) is outside [0, n_styles) only gets its fake_px.  Returns (fake_px, part, hits);
+    all three may be passed in to be reused."""
+    _check_dev(fake_norm, real_px, mean, std, fake_px)
+    assert fake_norm.dim() == 3 and fake_norm.shape == real_px.shape
+    fake_norm, real_px = fake_norm.contiguous(), real_px.contiguous()
+    B, T, Fd = fake_norm.shape
+    mean, std = mean.contiguous(), std.contiguous()
+    assert mean.numel() == Fd and std.numel() == Fd
+    _check_int(style, torch.int32, (B,), 'style')
+    assert hist.dim() == 3 and hist.shape[0] == n_styles and hist.shape[1] == 4
+    _check_int(hist, torch.int64, tuple(hist.shape), 'hist')
+    if fake_px is None:
+        fake_px = torch.empty(B, T, Fd, device=fake_norm.device)
+    if part is None:
+        part = torch.empty(B, 3, dtype=torch.float64, device=fake_norm.device)
+    if hits is None:
+        hits = torch.empty(B, dtype=torch.int32, device=fake_norm.device)
+    assert fake_px.is_contiguous() and tuple(fake_px.shape) == (B, T, Fd)
+    _check_f64(part, (B, 3), 'part')
+    _check_int(hits, torch.int32, (B,), 'hits')
+    N.check(N.lib.a2m_eval_clip_f32(_p(fake_norm), _p(real_px), _p(style), _p(mean), _p(std), B, T, Fd, n_styles,
+                                    float(alpha), hist.shape[2], float(speed_width), float(accel_width),
+                                    _p(fake_px), _p(part), _p(hits), _p(hist), _stream()))
+    return fake_px, part, hits
+
+
+def eval_gram(fake_px, real_px, style, sx, gram):
+    """The second launch (a2m_eval_gram_f64): adds the sums of x and of x x^T over the frames of each
+    style's clips to sx [n_styles, 2, F] and gram [n_styles, 2, F, F] (float64; real, then
+    generated), in float64 on the MFMA unit.  Only the 16 x 16 tiles on and above gram's diagonal
+    are written.  Returns (sx, gram)."""
+    _check_dev(fake_px, real_px)
+    assert fake_px.dim() == 3 and fake_px.shape == real_px.shape
+    fake_px, real_px = fake_px.contiguous(), real_px.contiguous()
+    B, T, Fd = fake_px.shape
+    n_styles = sx.shape[0]
+    _check_int(style, torch.int32, (B,), 'style')
+    _check_f64(sx, (n_styles, 2, Fd), 'sx')
+    _check_f64(gram, (n_styles, 2, Fd, Fd), 'gram')
+    N.check(N.lib.a2m_eval_gram_f64(_p(fake_px), _p(real_px), _p(style), B, T, Fd, n_styles, _p(sx), _p(gram),
+                                    _stream()))
+    return sx, gram
+
+
+def eval_finish(part, hits, style, T, counts, sums):
+    """The third launch (a2m_eval_finish_f64): adds eval_clip's part [B, 3] and hits [B], clips
+    ascending, to counts [3 n_styles + 1] (int64: per style clips, frames, hits; then the clips
+    whose style is out of range) and sums [n_styles, 3] (float64: per style L1, real speed,
+    generated speed).  Returns (counts, sums)."""
+    B = part.shape[0]
+    n_styles = sums.shape[0]
+    _check_f64(part, (B, 3), 'part')
+    _check_int(hits, torch.int32, (B,), 'hits')
+    _check_int(style, torch.int32, (B,), 'style')
+    _check_int(counts, torch.int64, (3 * n_styles + 1,), 'counts')
+    _check_f64(sums, (n_styles, 3), 'sums')
+    N.check(N.lib.a2m_eval_finish_f64(_p(part), _p(hits), _p(style), B, T, n_styles, _p(counts), _p(sums),
+                                      _stream()))
+    return counts, sums
+
+
 def gather_segments_(dst, segments):
     """dst[off:off + t.numel()] = t.reshape(-1) for every (off, t) in segments (contiguous fp32
     device tensors), 48 segments per launch (a2m_gather_segments_f32)."""

@@ -684,6 +684,38 @@ int a2m_val_finish_f32(const double* part, int32_t B, int32_t T, int32_t Fd, con
                        int32_t L, const float* bone, const float* angle, float lambda_gan,
                        float lambda_d, double* acc, void* stream);
 
+/* The evaluation pass over one batch of a split (a2m.evaluation.PoseEvaluator) in
+ * three launches.  Poses are [B][T][F] contiguous, a frame being its x row then its y row of
+ * K = F / 2 keypoints; style [B] (int32) names each clip's accumulators, and a clip whose style is
+ * outside [0, n_styles) is left out of every metric and counted as dropped.  Every floating-point
+ * sum runs in float64 in a fixed order with no atomics; only the integer histogram counters are
+ * updated with atomicAdd.  The accumulators are never overwritten: zero them once per pass.
+ * a2m_eval_clip_f32: fake_px = fake_norm * std + mean (two float32 roundings, as
+ * a2m_pose_denormalize_f32; written for every clip).  Per counted clip: hits [B] = the keypoints of
+ * all frames within alpha * max(x extent, y extent) of the real frame (float64 on the float32
+ * coordinates, <=, as a2m_pck_f32); part [B][3] (float64) = the sums of |fake_px - real_px|, of the
+ * real and of the generated speeds.  The speed of frame t >= 1 is the mean over joints 1..K-1 of
+ * |p[t] - p[t-1]|, the acceleration of t >= 2 that of |p[t] - 2 p[t-1] + p[t-2]|, in float64; each
+ * is counted in bin min(floor(v / width), n_bins - 1) of hist [n_styles][4][n_bins] (int64; real
+ * speed, generated speed, real acceleration, generated acceleration).  One workgroup per clip;
+ * T >= 1 (no upper bound), F even, 4 <= F <= 2560, T * F < 2^31.
+ * a2m_eval_gram_f64: adds to sx [n_styles][2][F] and gram [n_styles][2][F][F] (float64; real, then
+ * generated) the sums of x and of x x^T over the frames of each style's clips, float64 products and
+ * sums on the MFMA unit.  Only the 16 x 16 tiles on and above the diagonal are written
+ * (gram[i][j] with i / 16 <= j / 16); the rest is the mirror image.  Each tile has one owning wave,
+ * which takes the clips in ascending order and a clip's frames in ascending steps of 4.
+ * a2m_eval_finish_f64: adds the clips' partials, clips ascending, to counts [3 n_styles + 1]
+ * (int64; per style clips, frames, hits, then the dropped clips) and sums [n_styles][3] (float64;
+ * per style L1, real speed, generated speed).  One wave. */
+int a2m_eval_clip_f32(const float* fake_norm, const float* real_px, const int32_t* style, const float* mean,
+                      const float* std_, int32_t B, int32_t T, int32_t F, int32_t n_styles, double alpha,
+                      int32_t n_bins, double speed_width, double accel_width, float* fake_px, double* part,
+                      int32_t* hits, int64_t* hist, void* stream);
+int a2m_eval_gram_f64(const float* fake_px, const float* real_px, const int32_t* style, int32_t B, int32_t T,
+                      int32_t F, int32_t n_styles, double* sx, double* gram, void* stream);
+int a2m_eval_finish_f64(const double* part, const int32_t* hits, const int32_t* style, int32_t B, int32_t T,
+                        int32_t n_styles, int64_t* counts, double* sums, void* stream);
+
 /* General strided GEMM on the same MFMA engine (linear layers' backward, 1x1 projections):
  *   C[m][n] (+)= alpha * sum_k A(m,k) B(n,k) (+ bias[m]), per batch z < batch
  *   n = n0*N1 + n1, k = k0*K1 + k1 (two-level index spaces cover [B][C][T] row sets)
