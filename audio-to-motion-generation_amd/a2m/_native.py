@@ -154,6 +154,8 @@ SIGNATURES = {
     'a2m_eval_clip_f32': (ctypes.c_int, [P, P, P, P, P, I32, I32, I32, I32, F64, I32, F64, F64, P, P, P, P, P]),
     'a2m_eval_gram_f64': (ctypes.c_int, [P, P, P, I32, I32, I32, I32, P, P, P]),
     'a2m_eval_finish_f64': (ctypes.c_int, [P, P, P, I32, I32, I32, P, P, P]),
+    'a2m_eval_sync_f64': (ctypes.c_int, [P, P, P, P, P, I32, I32, I32, I32, I32, I32, I32, F64, P, P, P, P, P, P]),
+    'a2m_eval_sync_finish_f64': (ctypes.c_int, [P, P, I32, I32, I32, I32, P, P, P]),
     'a2m_adam_f32': (ctypes.c_int, [P, P, P, P, I64, F32, F32, F32, F32, F32, I32, P]),
     'a2m_adam_dev_f32': (ctypes.c_int, [P, P, P, P, I64, P, F32, F32, F32, F32, P, P]),
     'a2m_gather_segments_f32': (ctypes.c_int, [P, P, P, I32, P, P]),

@@ -25,6 +25,32 @@ distributions.  The reference has PCK only; the other metrics are a2m's own defi
 The histogram range (speed_max = accel_max = 64 px / frame in 512 bins) is a guess, nobody has
 looked at PATS speeds at 15 fps: the last bin catches everything beyond it, and its share of the
 samples is reported as speed_overflow / accel_overflow.  Widen the range when that share is large.
+
+AudioSyncEvaluator / evaluate(..., sync=True): none of the metrics above reads the audio, so a
+generator whose gestures ignore the speech scores like one whose strokes land on the syllables.
+The opt-in synchrony metrics (SYNC_METRICS) do, again a2m's own definitions, float64
+on the float32 inputs, per clip of frames 0..T-1:
+
+  onset     o[t] = (1/C) sum_c max(0, (a[t,c] - a[t-1,c]) sigma_c), t = 1..T-1; a the audio feature
+            the generator got, sigma_c = audio_std[c] when it was standardised (else 1), so that the
+            onsets are those of the raw log-mel whatever the generator was trained with
+  speed     s[t] as above, of the real and of the generated pose
+  beats     audio at t in [2, T-2]: o[t] > o[t-1], o[t] >= o[t+1] and o[t] > onset_delta mean(o[1..T-1]);
+            motion (kinematic) at t in [2, T-2]: s[t] < s[t-1] and s[t] <= s[t+1].  A constant signal
+            has none, nor has a clip of T < 4
+  beat_dist every motion beat's distance in frames to the clip's nearest audio beat, counted in bin
+            min(d, n_dist - 1), the last bin also when the clip has no audio beat; and the reverse
+            direction, every audio beat to the nearest motion beat, the same way
+  beat_align_*   sum_d h[d] exp(-d^2 / (2 beat_sigma^2)) / sum_d h[d] over motion->audio (AIST++'s
+                 direction); beat_recall_* the same over audio->motion
+  sync_corr_*    Pearson's r of the pairs (o[t], s[t+l]), t and t + l in [1, T-1], for l = -n_lags ..
+                 n_lags, from float64 sums; NaN with fewer than 2 pairs or no variance
+  sync_lag_*     the l of the largest r; l > 0: the motion follows the audio
+
+each for the real pose (the ceiling a generator can be held to) and the generated one.
+onset_delta = 1.0 and beat_sigma = 1.0 frame (67 ms at 15 fps; AIST++ uses 50 ms) are guesses like
+the histogram range: nobody has looked at PATS onsets at 15 fps.  beat_far_share is the share of
+the motion beats in the last distance bin.
 """
 import numpy as np
 import torch
@@ -34,6 +60,9 @@ from ._native import check, lib
 
 METRICS = ('pck', 'l1', 'fd', 'w1_speed', 'w1_accel', 'mean_speed_real', 'mean_speed_fake', 'n_clips',
            'n_frames', 'speed_overflow', 'accel_overflow')
+SYNC_METRICS = ('beat_align_real', 'beat_align_fake', 'beat_recall_real', 'beat_recall_fake', 'sync_corr_real',
+                'sync_corr_fake', 'sync_lag_real', 'sync_lag_fake', 'n_audio_beats', 'n_motion_beats_real',
+                'n_motion_beats_fake', 'beat_far_share')
 
 
 def compute_pck(pred, gt, alpha=0.2):
@@ -108,6 +137,45 @@ def _metrics(counts, sums, hist, sx, gram, K, speed_width, accel_width):
     return out
 
 
+def beat_alignment(hist, beat_sigma=1.0):
+    """sum_d h[d] exp(-d^2 / (2 beat_sigma^2)) / sum_d h[d] of a histogram of beat distances in frames
+    (bin d holds distance d; the last bin everything farther, and the beats with no partner);
+    NaN for an empty histogram."""
+    h = np.asarray(hist, np.float64)
+    if h.sum() <= 0:
+        return float('nan')
+    d = np.arange(h.shape[-1], dtype=np.float64)
+    return float((h * np.exp(-d * d / (2.0 * float(beat_sigma) ** 2))).sum() / h.sum())
+
+
+def pearson_from_sums(n, sx, sxx, sy, syy, sxy):
+    """Pearson's r per element from counts and float64 sums: (n sxy - sx sy) / sqrt((n sxx - sx^2)
+    (n syy - sy^2)); NaN where n < 2 or a variance is <= 0."""
+    n, sx, sxx, sy, syy, sxy = (np.asarray(a, np.float64) for a in (n, sx, sxx, sy, syy, sxy))
+    vx, vy = n * sxx - sx * sx, n * syy - sy * sy
+    ok = (n >= 2) & (vx > 0) & (vy > 0)
+    r = np.full(np.broadcast(n, vx).shape, np.nan)
+    r[ok] = ((n * sxy - sx * sy)[ok]) / np.sqrt(vx[ok] * vy[ok])
+    return r
+
+
+def _sync_metrics(beat_dist, beat_counts, lag_sums, lag_n, beat_sigma):
+    """One entry of AudioSyncEvaluator.result() from one style's (or the pooled) accumulators."""
+    nan = float('nan')
+    n_lags = (len(lag_n) - 1) // 2
+    out = {'n_audio_beats': int(beat_counts[0]), 'n_motion_beats_real': int(beat_counts[1]),
+           'n_motion_beats_fake': int(beat_counts[2])}
+    for w, name in enumerate(('real', 'fake')):
+        out['beat_align_' + name] = beat_alignment(beat_dist[w, 0], beat_sigma)
+        out['beat_recall_' + name] = beat_alignment(beat_dist[w, 1], beat_sigma)
+        r = pearson_from_sums(lag_n, lag_sums[:, 0], lag_sums[:, 1], *(lag_sums[:, 2 + 3 * w + j] for j in range(3)))
+        out['sync_corr_' + name] = [float(v) for v in r]
+        out['sync_lag_' + name] = nan if np.isnan(r).all() else int(np.nanargmax(r)) - n_lags
+    m2a = beat_dist[:, 0]
+    out['beat_far_share'] = float(m2a[:, -1].sum()) / float(m2a.sum()) if m2a.sum() else nan
+    return out
+
+
 class PoseEvaluator:
     """The device accumulators of one evaluation pass.  pose_mean, pose_std [2K]: the statistics
     the generator's output is de-normalised with; n_styles: the number of speakers."""
@@ -171,6 +239,11 @@ class PoseEvaluator:
         F.eval_gram(fake_px, real_px, style, st['sx'], st['gram'])
         F.eval_finish(part, hits, style, T, st['counts'], st['sums'])
 
+    def fake_px(self, n, T):
+        """The de-normalised generated pose [n, T, 2K] that the last update() of a batch of this size
+        left on the device (read-only: the next such update() overwrites it)."""
+        return self._buffers[(n, T)][0]
+
     def result(self):
         """The pass's one host read.  {style id: metrics, ..., 'all': metrics, 'dropped': clips whose
         style was out of range}; metrics holds METRICS.  'all' comes from the summed accumulators
@@ -188,17 +261,90 @@ class PoseEvaluator:
         return out
 
 
+class AudioSyncEvaluator:
+    """The device accumulators of the audio-motion synchrony metrics of one evaluation pass (the
+    module docstring has the definitions).  n_styles: the number of speakers; n_lags: the lagged
+    correlation runs over -n_lags .. n_lags frames (0 <= n_lags <= 16); n_dist: the bins of the beat
+    distance histograms; audio_std [C]: the std the audio fed to update() was standardised with, or
+    None when it is raw."""
+
+    def __init__(self, n_styles, n_lags=4, n_dist=32, onset_delta=1.0, audio_std=None, device='cuda'):
+        if n_styles <= 0 or n_dist < 2 or not 0 <= n_lags <= 16:
+            raise ValueError('n_styles must be positive, n_dist >= 2 and 0 <= n_lags <= 16')
+        if not (np.isfinite(onset_delta) and onset_delta >= 0):
+            raise ValueError('onset_delta must be finite and >= 0')
+        self.device = torch.device(device)
+        self.n_styles, self.n_lags, self.n_dist = int(n_styles), int(n_lags), int(n_dist)
+        self.onset_delta = float(onset_delta)
+        self.audio_std = None if audio_std is None else \
+            torch.as_tensor(audio_std).to(self.device, torch.float32).contiguous().reshape(-1)
+        S, L = self.n_styles, 2 * self.n_lags + 1
+        # one float64 arena, as PoseEvaluator's: result() is one read
+        sizes = [('beat_dist', (S, 2, 2, self.n_dist), torch.int64), ('beat_counts', (S, 3), torch.int64),
+                 ('lag_sums', (S, L, 8), torch.float64), ('lag_n', (S, L), torch.int64)]
+        self._layout, n = [], 0
+        for name, shape, dtype in sizes:
+            self._layout.append((name, n, shape, dtype))
+            n += int(np.prod(shape))
+        self._arena = torch.zeros(n, dtype=torch.float64, device=self.device)
+        self._state = self._views(self._arena)
+        self._buffers = {}
+
+    _views = PoseEvaluator._views
+
+    def reset(self):
+        self._arena.zero_()
+
+    def state(self):
+        """The raw accumulators as device tensors (views, not copies): beat_dist [n_styles, 2, 2,
+        n_dist] (real | generated pose; motion->audio | audio->motion), beat_counts [n_styles, 3]
+        (audio, real motion, generated motion beats), lag_sums [n_styles, 2 n_lags + 1, 8] (per lag
+        the sums of o, o^2, then s, s^2, o s of the real and of the generated pose) and lag_n
+        [n_styles, 2 n_lags + 1] (the pairs)."""
+        return dict(self._state)
+
+    def update(self, audio, fake_px, real_px, style):
+        """Adds one batch: audio [n, T, C] as the generator got it, fake_px and real_px [n, T, 2K]
+        in pixels, style int32 [n] on the device.  Two launches, no host synchronisation, and no
+        allocation after the first batch of a size."""
+        n, T = audio.shape[:2]
+        if self.audio_std is not None and self.audio_std.numel() != audio.shape[2]:
+            raise ValueError(f'audio of {audio.shape[2]} columns; audio_std has {self.audio_std.numel()}')
+        if n not in self._buffers:
+            self._buffers[n] = torch.empty(n, 2 * self.n_lags + 1, 8, dtype=torch.float64, device=self.device)
+        part, st = self._buffers[n], self._state
+        F.eval_sync(audio, fake_px, real_px, style, st['beat_dist'], st['beat_counts'], self.n_lags,
+                    self.onset_delta, self.audio_std, part)
+        F.eval_sync_finish(part, style, T, st['lag_sums'], st['lag_n'])
+
+    def result(self, beat_sigma=1.0):
+        """The one host read.  {style id: metrics, ..., 'all': metrics}; metrics holds SYNC_METRICS.
+        beat_sigma: the Gaussian width in frames of beat_align / beat_recall, a host-side choice.
+        'all' comes from the summed accumulators.  A style without beats or pairs has NaN metrics."""
+        host = {k: v.numpy() for k, v in self._views(self._arena.cpu()).items()}
+        keys = ('beat_dist', 'beat_counts', 'lag_sums', 'lag_n')
+        out = {s: _sync_metrics(*(host[k][s] for k in keys), beat_sigma) for s in range(self.n_styles)}
+        out['all'] = _sync_metrics(*(host[k].sum(0) for k in keys), beat_sigma)
+        return out
+
+
 def evaluate(generator, loader, split='test', pose_mean=None, pose_std=None, audio_mean=None, audio_std=None,
-             **evaluator_kwargs):
+             sync=False, sync_kwargs=None, beat_sigma=1.0, **evaluator_kwargs):
     """One evaluation pass of `generator` over a split of a PatsLoader: result() of a PoseEvaluator,
     keyed by speaker name (loader.speaker_dict), 'all' and 'dropped'.  pose_mean, pose_std: the
     statistics the generator was trained with (its output is de-normalised with them);
     audio_mean, audio_std: the audio is standardised with them when given.  The real poses come
     neck-subtracted and not normalised, as generate_motion_video.py:247-251 compares them.  The
-    generator runs in eval mode under no_grad and gets its training flags back."""
+    generator runs in eval mode under no_grad and gets its training flags back.
+    sync=True adds the SYNC_METRICS of an AudioSyncEvaluator(**sync_kwargs) to every speaker's entry
+    and to 'all' (two more launches a batch and a second host read after the last batch); it gets
+    the audio the generator got and the audio_std it was standardised with.  beat_sigma: see
+    AudioSyncEvaluator.result."""
     if pose_mean is None or pose_std is None:
         raise ValueError('evaluate needs pose_mean and pose_std')
     ev = PoseEvaluator(pose_mean, pose_std, len(loader.speaker_dict), device=loader.device, **evaluator_kwargs)
+    sev = AudioSyncEvaluator(len(loader.speaker_dict), audio_std=audio_std, device=loader.device,
+                             **(sync_kwargs or {})) if sync else None
     zero, one = torch.zeros_like(ev.mean), torch.ones_like(ev.std)
     flags = [(m, m.training) for m in generator.modules()]
     generator.eval()
@@ -207,10 +353,15 @@ def evaluate(generator, loader, split='test', pose_mean=None, pose_std=None, aud
             for audio, real_px, style in loader.pairs(split, zero, one, audio_mean, audio_std, with_style=True):
                 fake = generator(audio)
                 ev.update(fake[0] if isinstance(fake, (tuple, list)) else fake, real_px, style)
+                if sev is not None:
+                    sev.update(audio, ev.fake_px(*real_px.shape[:2]), real_px, style)
     finally:
         for m, flag in flags:
             m.training = flag
     res = ev.result()
+    if sev is not None:
+        for key, extra in sev.result(beat_sigma).items():
+            res[key].update(extra)
     out = {name: res[i] for name, i in loader.speaker_dict.items()}
     out['all'], out['dropped'] = res['all'], res['dropped']
     return out

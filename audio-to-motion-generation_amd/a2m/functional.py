@@ -1262,6 +1262,60 @@ def eval_finish(part, hits, style, T, counts, sums):
     return counts, sums
 
 
+def eval_sync(audio, fake_px, real_px, style, beat_dist, beat_counts, n_lags=4, onset_delta=1.0, audio_std=None,
+              part=None, onset_out=None, speed_out=None):
+    """The first launch of the audio-motion synchrony metrics (a2m_eval_sync_f64): per clip the onset
+    strength of audio [B, T, C] (audio_std [C]: the std it was standardised with, or None) and the
+    speeds of real_px and fake_px [B, T, F], their beats, every beat's distance to the nearest beat
+    of the other kind counted in beat_dist [n_styles, 2, 2, n_dist] (int64, added to), the beats in
+    beat_counts [n_styles, 3] (int64, added to), and part [B, 2 n_lags + 1, 8] (float64), the clip's
+    lagged sums.  onset_out [B, T] and speed_out [B, 2, T] (float64), when given, get the series.
+    Returns part, which may be passed in to be reused."""
+    _check_dev(audio, fake_px, real_px, audio_std)
+    assert audio.dim() == 3 and fake_px.dim() == 3 and fake_px.shape == real_px.shape
+    assert audio.shape[:2] == fake_px.shape[:2], (tuple(audio.shape), tuple(fake_px.shape))
+    audio, fake_px, real_px = audio.contiguous(), fake_px.contiguous(), real_px.contiguous()
+    B, T, C = audio.shape
+    Fd = fake_px.shape[2]
+    if audio_std is not None:
+        audio_std = audio_std.contiguous()
+        assert audio_std.numel() == C
+    _check_int(style, torch.int32, (B,), 'style')
+    assert beat_dist.dim() == 4 and tuple(beat_dist.shape[1:3]) == (2, 2)
+    n_styles, n_dist = beat_dist.shape[0], beat_dist.shape[3]
+    _check_int(beat_dist, torch.int64, tuple(beat_dist.shape), 'beat_dist')
+    _check_int(beat_counts, torch.int64, (n_styles, 3), 'beat_counts')
+    L = 2 * int(n_lags) + 1
+    if part is None:
+        part = torch.empty(B, L, 8, dtype=torch.float64, device=audio.device)
+    _check_f64(part, (B, L, 8), 'part')
+    if onset_out is not None:
+        _check_f64(onset_out, (B, T), 'onset_out')
+    if speed_out is not None:
+        _check_f64(speed_out, (B, 2, T), 'speed_out')
+    N.check(N.lib.a2m_eval_sync_f64(_p(audio), _p(fake_px), _p(real_px), _p(style), _p(audio_std), B, T, C, Fd,
+                                    n_styles, int(n_lags), n_dist, float(onset_delta), _p(beat_dist),
+                                    _p(beat_counts), _p(part), _p(onset_out), _p(speed_out), _stream()))
+    return part
+
+
+def eval_sync_finish(part, style, T, lag_sums, lag_n):
+    """The second launch (a2m_eval_sync_finish_f64): adds eval_sync's part [B, 2 n_lags + 1, 8], clips
+    ascending, per style to lag_sums [n_styles, 2 n_lags + 1, 8] (float64) and the pair counts,
+    max(T - 1 - |l|, 0) per counted clip, to lag_n [n_styles, 2 n_lags + 1] (int64).  Returns
+    (lag_sums, lag_n)."""
+    assert part.dim() == 3 and part.shape[1] % 2 == 1 and part.shape[2] == 8
+    B, L = part.shape[:2]
+    n_styles = lag_sums.shape[0]
+    _check_f64(part, (B, L, 8), 'part')
+    _check_int(style, torch.int32, (B,), 'style')
+    _check_f64(lag_sums, (n_styles, L, 8), 'lag_sums')
+    _check_int(lag_n, torch.int64, (n_styles, L), 'lag_n')
+    N.check(N.lib.a2m_eval_sync_finish_f64(_p(part), _p(style), B, T, n_styles, L // 2, _p(lag_sums), _p(lag_n),
+                                           _stream()))
+    return lag_sums, lag_n
+
+
 def gather_segments_(dst, segments):
     """dst[off:off + t.numel()] = t.reshape(-1) for every (off, t) in segments (contiguous fp32
     device tensors), 48 segments per launch (a2m_gather_segments_f32)."""

@@ -5,10 +5,15 @@
 //   eval_gram    per style, for the real and for the generated frames: sum x and sum x x^T in
 //                fp64 (v_mfma_f64_16x16x4_f64), the inputs of the Frechet distance
 //   eval_finish  the clips' partials into the per-style accumulators
+// and the two of the opt-in audio-motion synchrony metrics (a2m.evaluation.AudioSyncEvaluator):
+//   eval_sync         per clip the onset strength of the audio and the speeds of both poses, their
+//                     beats, the beat distance histograms and the lagged sums of (onset, speed)
+//   eval_sync_finish  the clips' lagged sums into the per-style accumulators
 // Every floating-point sum runs in a fixed order with no atomics; the histogram counters are
 // integers (atomicAdd, whose result does not depend on the order).  Nothing is read back: the
 // host reads the accumulators once, at the end of the pass.
 #include <algorithm>
+#include <cfloat>
 
 #include "a2m_internal.h"
 
@@ -23,6 +28,14 @@ constexpr size_t kEvalLds = 60 << 10;   // dynamic LDS of one workgroup (the sta
 constexpr int kEvalLoads = 8;           // loads of each pose a thread keeps in flight while a trip's rows come in
 constexpr int kGramSteps = 16;          // MFMA steps (of 4 frames) per chunk of the Gram walk
 constexpr int kGramDepth = 4;           // chunks whose loads are in flight ahead of the MFMAs
+
+constexpr int kSyncThreads = 256;
+constexpr int kSyncCols = 4;            // audio columns a lane carries in registers: C <= 256 is read once
+// 25 B of dynamic LDS a frame (onset and two speeds as doubles, a flag byte): 51,200 B at 2048, on top of
+// 32 B static, under the 64 KB a workgroup gets without asking for more
+constexpr int kSyncMaxT = 2048;
+constexpr int kSyncMaxLags = 16;
+constexpr int kSyncFinishLoads = 8;     // clips whose partials the finish kernel keeps in flight
 
 typedef double double4_t __attribute__((ext_vector_type(4)));
 
@@ -338,6 +351,190 @@ __global__ __launch_bounds__(kEvalFinishThreads) void eval_finish_kernel(
   }
 }
 
+__device__ __forceinline__ double eval_wave_sum(double v) {
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+  return v;
+}
+
+// distance from frame t to the nearest frame whose flags hold `bit`, n_dist - 1 (the catch-all bin)
+// where there is none closer
+__device__ __forceinline__ int sync_nearest(const unsigned char* flags, int t, int T, int bit, int n_dist) {
+  for (int d = 0; d < n_dist - 1; ++d) {
+    const int lo = t - d, hi = t + d;
+    if ((lo >= 0 && (flags[lo] & bit)) || (hi < T && (flags[hi] & bit))) return d;
+  }
+  return n_dist - 1;
+}
+
+// One workgroup per clip.  Its three series sit in LDS as doubles: the onset strength o (each wave
+// a contiguous run of frames, lanes over the audio columns, the previous row carried in registers,
+// the column sum a butterfly) and the speeds of both poses (a quad per frame, eval_clip's
+// eval_motion_norm).  Then a thread per frame: the beat flags (bit 0 audio, 1 real motion, 2
+// generated motion), and from every beat an outward scan for the nearest beat of the other kind.
+// The lagged sums take a wave per lag, lanes striding t ascending, then the butterfly.  Every
+// floating-point sum has a fixed order; the histogram and beat counters are integers.
+__global__ __launch_bounds__(kSyncThreads) void eval_sync_kernel(
+    const float* __restrict__ audio, const float* __restrict__ fake_px, const float* __restrict__ real_px,
+    const int32_t* __restrict__ style, const float* __restrict__ audio_std, int T, int C, int K, int n_styles,
+    int n_lags, int n_dist, double onset_delta, unsigned long long* __restrict__ beat_dist,
+    unsigned long long* __restrict__ beat_counts, double* __restrict__ part, double* __restrict__ onset_out,
+    double* __restrict__ speed_out) {
+  extern __shared__ __attribute__((aligned(16))) double sync_lds[];
+  __shared__ double red[kSyncThreads / 64];
+  double* o = sync_lds;
+  double* sr = o + T;
+  double* sf = sr + T;
+  unsigned char* flags = reinterpret_cast<unsigned char*>(sf + T);
+  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6, F = 2 * K;
+  const float* ap = audio + (int64_t)b * T * C;
+  const float* rp = real_px + (int64_t)b * T * F;
+  const float* fp = fake_px + (int64_t)b * T * F;
+  {
+    const int per = (T - 1 + kSyncThreads / 64 - 1) / (kSyncThreads / 64);
+    const int lo = 1 + w * per, hi = min(lo + per, T);    // this wave's frames [lo, hi)
+    int col[kSyncCols];
+    double sg[kSyncCols];                                 // 0 beyond C: that column adds nothing
+    float prev[kSyncCols], cur[kSyncCols], next[kSyncCols];
+#pragma unroll
+    for (int j = 0; j < kSyncCols; ++j) {
+      col[j] = min(lane + 64 * j, C - 1);
+      sg[j] = lane + 64 * j < C ? (audio_std ? (double)audio_std[col[j]] : 1.0) : 0.0;
+      prev[j] = lo < hi ? ap[(lo - 1) * C + col[j]] : 0.f;
+      cur[j] = lo < hi ? ap[lo * C + col[j]] : 0.f;
+    }
+    for (int t = lo; t < hi; ++t) {
+      double p = 0.0;
+#pragma unroll
+      for (int j = 0; j < kSyncCols; ++j) {   // the next row is in flight while this one is summed
+        next[j] = ap[min(t + 1, hi - 1) * C + col[j]];
+        p += fmax(0.0, ((double)cur[j] - (double)prev[j]) * sg[j]);
+        prev[j] = cur[j];
+        cur[j] = next[j];
+      }
+      for (int c = lane + 64 * kSyncCols; c < C; c += 64)   // wider than the registers: both rows from memory
+        p += fmax(0.0, ((double)ap[t * C + c] - (double)ap[(t - 1) * C + c]) * (audio_std ? (double)audio_std[c] : 1.0));
+      p = eval_wave_sum(p);
+      if (lane == 0) o[t] = p / (double)C;
+    }
+  }
+  if (tid == 0) o[0] = sr[0] = sf[0] = 0.0;
+  for (int t = 1 + (tid >> 2); t < T; t += kSyncThreads / 4) {   // uniform over a quad
+    const double vr = eval_motion_norm(rp + t * F, rp + (t - 1) * F, nullptr, K, tid & 3);
+    const double vf = eval_motion_norm(fp + t * F, fp + (t - 1) * F, nullptr, K, tid & 3);
+    if ((tid & 3) == 0) {
+      sr[t] = vr;
+      sf[t] = vf;
+    }
+  }
+  __syncthreads();
+  for (int t = tid; t < T; t += kSyncThreads) {
+    if (onset_out) onset_out[(int64_t)b * T + t] = o[t];
+    if (speed_out) {
+      speed_out[(int64_t)(2 * b) * T + t] = sr[t];
+      speed_out[(int64_t)(2 * b + 1) * T + t] = sf[t];
+    }
+  }
+  const int st = style[b];
+  if (st < 0 || st >= n_styles) return;                   // uniform over the workgroup
+  double m = 0.0;
+  for (int t = 1 + tid; t < T; t += kSyncThreads) m += o[t];
+  m = eval_block_sum(m, red);
+  const double thr = T > 1 ? onset_delta * (m / (double)(T - 1)) : 0.0;
+  int na = 0, nr = 0, nf = 0;                             // this wave's beats
+  for (int t0 = 0; t0 < T; t0 += kSyncThreads) {          // whole trips: the ballots want every lane
+    const int t = t0 + tid;
+    int bits = 0;
+    if (t >= 2 && t <= T - 2) {
+      bits = (o[t] > o[t - 1] && o[t] >= o[t + 1] && o[t] > thr ? 1 : 0) |
+             (sr[t] < sr[t - 1] && sr[t] <= sr[t + 1] ? 2 : 0) | (sf[t] < sf[t - 1] && sf[t] <= sf[t + 1] ? 4 : 0);
+    }
+    if (t < T) flags[t] = (unsigned char)bits;
+    na += __popcll(__ballot(bits & 1));
+    nr += __popcll(__ballot(bits & 2));
+    nf += __popcll(__ballot(bits & 4));
+  }
+  if (lane == 0) {
+    if (na) atomicAdd(beat_counts + 3 * st, (unsigned long long)na);
+    if (nr) atomicAdd(beat_counts + 3 * st + 1, (unsigned long long)nr);
+    if (nf) atomicAdd(beat_counts + 3 * st + 2, (unsigned long long)nf);
+  }
+  __syncthreads();
+  unsigned long long* h = beat_dist + (int64_t)st * 4 * n_dist;   // [real | generated][motion->audio | audio->motion]
+  for (int t = 2 + tid; t <= T - 2; t += kSyncThreads) {
+    const int bits = flags[t];
+    if (bits & 2) eval_hist_add(h, sync_nearest(flags, t, T, 1, n_dist));
+    if (bits & 1) eval_hist_add(h + n_dist, sync_nearest(flags, t, T, 2, n_dist));
+    if (bits & 4) eval_hist_add(h + 2 * n_dist, sync_nearest(flags, t, T, 1, n_dist));
+    if (bits & 1) eval_hist_add(h + 3 * n_dist, sync_nearest(flags, t, T, 4, n_dist));
+  }
+  const int L = 2 * n_lags + 1;
+  for (int li = w; li < L; li += kSyncThreads / 64) {     // a wave owns a lag: no workgroup barrier per sum
+    const int l = li - n_lags;
+    const int hi = min(T - 1, T - 1 - l);                 // the pairs (o[t], s[t + l]), max(1, 1 - l) <= t <= hi
+    double so = 0.0, soo = 0.0, s1 = 0.0, s11 = 0.0, so1 = 0.0, s2 = 0.0, s22 = 0.0, so2 = 0.0;
+    for (int t = max(1, 1 - l) + lane; t <= hi; t += 64) {
+      const double x = o[t], yr = sr[t + l], yf = sf[t + l];
+      so += x;
+      soo += x * x;
+      s1 += yr;
+      s11 += yr * yr;
+      so1 += x * yr;
+      s2 += yf;
+      s22 += yf * yf;
+      so2 += x * yf;
+    }
+    so = eval_wave_sum(so);
+    soo = eval_wave_sum(soo);
+    s1 = eval_wave_sum(s1);
+    s11 = eval_wave_sum(s11);
+    so1 = eval_wave_sum(so1);
+    s2 = eval_wave_sum(s2);
+    s22 = eval_wave_sum(s22);
+    so2 = eval_wave_sum(so2);
+    if (lane == 0) {
+      double* p = part + ((int64_t)b * L + li) * 8;
+      p[0] = so;
+      p[1] = soo;
+      p[2] = s1;
+      p[3] = s11;
+      p[4] = so1;
+      p[5] = s2;
+      p[6] = s22;
+      p[7] = so2;
+    }
+  }
+}
+
+// One wave, as eval_finish_kernel.  Per style a lane owns an element of [2 n_lags + 1][8] and adds
+// the clips' partials to it in ascending clip order; lag_n gets the pair count of each lag by its
+// formula.  Every clip's row of part is loaded, so that the loads do not wait for the style test, and
+// a clip of another style adds 0 by a select.  That reads, on purpose, the rows of dropped clips,
+// which eval_sync_kernel never wrote: whatever bits they hold (a NaN too) are discarded unused.
+__global__ __launch_bounds__(kEvalFinishThreads) void eval_sync_finish_kernel(
+    const double* __restrict__ part, const int32_t* __restrict__ style, int B, int T, int n_styles, int n_lags,
+    double* __restrict__ lag_sums, long long* __restrict__ lag_n) {
+  const int lane = threadIdx.x, L = 2 * n_lags + 1, E = 8 * L;
+  for (int st = 0; st < n_styles; ++st) {
+    long long nc = 0;
+    for (int b = lane; b < B; b += kEvalFinishThreads) nc += style[b] == st;
+    for (int o = 32; o > 0; o >>= 1) nc += __shfl_xor(nc, o);
+    if (!nc) continue;                                    // uniform: no clip of this style in the batch
+    for (int e0 = 0; e0 < E; e0 += kEvalFinishThreads) {
+      const int e = min(e0 + lane, E - 1);
+      double acc = 0.0;
+      for (int b0 = 0; b0 < B; b0 += kSyncFinishLoads) {
+        double v[kSyncFinishLoads];
+#pragma unroll
+        for (int u = 0; u < kSyncFinishLoads; ++u) v[u] = part[(int64_t)min(b0 + u, B - 1) * E + e];
+#pragma unroll
+        for (int u = 0; u < kSyncFinishLoads; ++u) acc += b0 + u < B && style[b0 + u] == st ? v[u] : 0.0;
+      }
+      if (e0 + lane < E) lag_sums[(int64_t)st * E + e] += acc;
+    }
+    if (lane < L) lag_n[(int64_t)st * L + lane] += nc * max(T - 1 - abs(lane - n_lags), 0);
+  }
+}
+
 }  // namespace
 }  // namespace a2m
 
@@ -388,6 +585,38 @@ int a2m_eval_finish_f64(const double* part, const int32_t* hits, const int32_t* 
                 "eval_finish: bad args");
   hipLaunchKernelGGL(eval_finish_kernel, dim3(1), dim3(kEvalFinishThreads), 0, as_stream(stream), part, hits,
                      style, B, T, n_styles, reinterpret_cast<long long*>(counts), sums);
+  A2M_LAUNCH_CHECK();
+  return A2M_OK;
+}
+
+int a2m_eval_sync_f64(const float* audio, const float* fake_px, const float* real_px, const int32_t* style,
+                      const float* audio_std, int32_t B, int32_t T, int32_t C, int32_t F, int32_t n_styles,
+                      int32_t n_lags, int32_t n_dist, double onset_delta, int64_t* beat_dist, int64_t* beat_counts,
+                      double* part, double* onset_out, double* speed_out, void* stream) {
+  A2M_CHECK_ARG(audio && fake_px && real_px && style && beat_dist && beat_counts && part && B > 0 && T >= 1 &&
+                    C > 0 && F >= 4 && F % 2 == 0 && n_styles > 0 && n_dist >= 2 && n_lags >= 0 &&
+                    n_lags <= kSyncMaxLags && onset_delta >= 0.0 && onset_delta <= DBL_MAX,
+                "eval_sync: bad args");
+  // the three series of a clip sit in LDS; the kernel indexes one clip with 32-bit ints
+  A2M_CHECK_ARG(T <= kSyncMaxT && (int64_t)T * C <= INT32_MAX && (int64_t)T * F <= INT32_MAX,
+                "eval_sync: T = %d, C = %d, F = %d beyond the kernel's limits (T <= 2048, T * C and T * F < 2^31)", T, C,
+                F);
+  const size_t lds = (3 * sizeof(double) + 1) * (size_t)T;
+  hipLaunchKernelGGL(eval_sync_kernel, dim3(B), dim3(kSyncThreads), lds, as_stream(stream), audio, fake_px, real_px,
+                     style, audio_std, T, C, F / 2, n_styles, n_lags, n_dist, onset_delta,
+                     reinterpret_cast<unsigned long long*>(beat_dist),
+                     reinterpret_cast<unsigned long long*>(beat_counts), part, onset_out, speed_out);
+  A2M_LAUNCH_CHECK();
+  return A2M_OK;
+}
+
+int a2m_eval_sync_finish_f64(const double* part, const int32_t* style, int32_t B, int32_t T, int32_t n_styles,
+                             int32_t n_lags, double* lag_sums, int64_t* lag_n, void* stream) {
+  A2M_CHECK_ARG(part && style && lag_sums && lag_n && B > 0 && T >= 1 && n_styles > 0 && n_lags >= 0 &&
+                    n_lags <= kSyncMaxLags,
+                "eval_sync_finish: bad args");
+  hipLaunchKernelGGL(eval_sync_finish_kernel, dim3(1), dim3(kEvalFinishThreads), 0, as_stream(stream), part, style,
+                     B, T, n_styles, n_lags, lag_sums, reinterpret_cast<long long*>(lag_n));
   A2M_LAUNCH_CHECK();
   return A2M_OK;
 }

@@ -716,6 +716,40 @@ int a2m_eval_gram_f64(const float* fake_px, const float* real_px, const int32_t*
 int a2m_eval_finish_f64(const double* part, const int32_t* hits, const int32_t* style, int32_t B, int32_t T,
                         int32_t n_styles, int64_t* counts, double* sums, void* stream);
 
+/* The audio-motion synchrony metrics of the same pass (a2m.evaluation.AudioSyncEvaluator; DESIGN.md
+ * 7.7), two launches a batch, opt-in.  audio [B][T][C] is the audio feature as the generator got
+ * it, audio_std [C] its standardisation's std or null (then 1); fake_px, real_px [B][T][F] and
+ * style [B] as above.  All arithmetic is float64 on the float32 inputs, every floating-point sum in
+ * a fixed order with no atomics; the integer counters are updated with atomicAdd.  A clip whose
+ * style is outside [0, n_styles) adds to no accumulator.  The accumulators are added to: zero them
+ * once per pass.
+ * a2m_eval_sync_f64, per clip and for t = 1..T-1:
+ *   onset o[t] = (1 / C) sum_c max(0, (audio[t][c] - audio[t-1][c]) * audio_std[c]),
+ *   speed s[t] as a2m_eval_clip_f32's, of the real and of the generated pose;
+ *   an audio beat at t in [2, T-2] where o[t] > o[t-1], o[t] >= o[t+1] and o[t] > onset_delta times the
+ *   clip's mean of o[1..T-1]; a motion beat where s[t] < s[t-1] and s[t] <= s[t+1].
+ *   beat_dist [n_styles][2][2][n_dist] (int64; real | generated pose, motion->audio | audio->motion)
+ *   counts every beat's distance in frames to the clip's nearest beat of the other kind in bin
+ *   min(d, n_dist - 1), the last bin also where there is none; beat_counts [n_styles][3] (int64) the
+ *   audio, real motion and generated motion beats.  part [B][2 n_lags + 1][8] (float64, written for
+ *   counted clips only): for the lag l = index - n_lags, over the pairs (o[t], s[t+l]) with t and t + l
+ *   in [1, T-1], the sums of o, o^2, then of s, s^2, o s for the real and again for the generated pose.
+ *   onset_out [B][T] and speed_out [B][2][T] (float64, real then generated, entry 0 zero; either may
+ *   be null) get the series of every clip.  One workgroup per clip, its series in LDS (25 B a
+ *   frame: three doubles and a flag byte, 51,200 B at the bound): T <= 2048;
+ *   F even and >= 4, n_dist >= 2, 0 <= n_lags <= 16, onset_delta finite and >= 0.
+ * a2m_eval_sync_finish_f64: adds part, clips ascending, per style to lag_sums
+ *   [n_styles][2 n_lags + 1][8] (float64), and to lag_n [n_styles][2 n_lags + 1] (int64) the number
+ *   of pairs, max(T - 1 - |l|, 0) per counted clip.  One wave.  It loads every clip's row of part,
+ *   the unwritten rows of dropped clips too, and discards those by a select: part must be B rows of
+ *   readable memory, whatever the dropped rows hold. */
+int a2m_eval_sync_f64(const float* audio, const float* fake_px, const float* real_px, const int32_t* style,
+                      const float* audio_std, int32_t B, int32_t T, int32_t C, int32_t F, int32_t n_styles,
+                      int32_t n_lags, int32_t n_dist, double onset_delta, int64_t* beat_dist, int64_t* beat_counts,
+                      double* part, double* onset_out, double* speed_out, void* stream);
+int a2m_eval_sync_finish_f64(const double* part, const int32_t* style, int32_t B, int32_t T, int32_t n_styles,
+                             int32_t n_lags, double* lag_sums, int64_t* lag_n, void* stream);
+
 /* General strided GEMM on the same MFMA engine (linear layers' backward, 1x1 projections):
  *   C[m][n] (+)= alpha * sum_k A(m,k) B(n,k) (+ bias[m]), per batch z < batch
  *   n = n0*N1 + n1, k = k0*K1 + k1 (two-level index spaces cover [B][C][T] row sets)
