@@ -34,6 +34,10 @@ SIGNATURES = {
     'a2m_pats_audio_num_frames': (I64, [I64, I32, I32, I32]),
     'a2m_pats_audio_f32': (ctypes.c_int, [P, I64, I64, I64, I32, I32, I32, I32, I32, P, I32, I32, F32,
                                           P, I64, P, P, P, P]),
+    'a2m_pats_audio_stream_f32': (ctypes.c_int, [P, I64, I64, I64, I32, I32, I32, I32, I32, P, I32, I32, F32,
+                                                 P, I64, P, P, P, P]),
+    'a2m_resample_stream_f32': (ctypes.c_int, [P, I64, I64, I64, I32, I32, I32, P, I64, I64, P, P]),
+    'a2m_track_blend_stream_f32': (ctypes.c_int, [P, I32, I32, I32, I32, P, I32, I32, P, P, P, P]),
     'a2m_resample_num_samples': (I64, [I64, I32, I32]),
     'a2m_resample_plan_bytes': (SZ, [I32, I32, I32, F64, F64]),
     'a2m_resample_plan_build': (ctypes.c_int, [I32, I32, I32, F64, F64, P, SZ]),

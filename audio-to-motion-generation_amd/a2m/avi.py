@@ -3,8 +3,9 @@ alone (generate_motion_video.py:203-207 hands this to ffmpeg).
 
   AVIWriter(path, W, H, fps, audio_rate)   hdrl (avih, a 'vids'/MJPG stream, an optional
                                            'auds' PCM mono s16le stream), movi ('00dc' per frame,
-                                           each followed by that frame's '01wb'), idx1
-  pcm16(wave)                              float [-1, 1] -> int16 samples
+                                           each followed by that frame's '01wb'), idx1;
+                                           the sound whole (set_audio) or as it comes (add_audio)
+  pcm16(wave)                             float [-1, 1] -> int16 samples
   read_avi(path)                           the files AVIWriter writes -> frames, sound, rates
   save_video_from_audio_video(wav, avi, out)   the reference's function: a PCM .wav under the
                                            picture of one of our .avi files
@@ -44,7 +45,8 @@ def _list(kind, payload):
 
 class AVIWriter:
     """write_frame(*pieces) appends one JPEG file (its pieces are written one after the other) as
-    a '00dc' chunk and, with audio_rate, the frame's share of the samples given to set_audio as a
+    a '00dc' chunk and, with audio_rate, the frame's share of the samples given to set_audio (the
+    whole track, before the first frame) or add_audio (in pieces, ahead of the frames) as a
     '01wb' chunk: frame i holds samples [floor(i sr scale / rate), floor((i + 1) sr scale / rate)),
     so no sample is lost or doubled, and the sound ends with the picture."""
 
@@ -62,7 +64,8 @@ class AVIWriter:
         self.audio_rate = None if audio_rate is None else int(audio_rate)
         self.frames, self.samples = 0, 0
         self._audio = np.zeros(0, '<i2')
-        self._index = []                     # (fourcc, offset from the 'movi' fourcc, size)
+        self._audio_off, self._streamed = 0, False   # add_audio: samples dropped so far; sound arrives in pieces
+        self._index = []                   # (fourcc, offset from the 'movi' fourcc, size)
         self._largest = [0, 0]               # largest video / audio chunk
         self._closed = False
         self.f = open(path, 'wb')
@@ -76,6 +79,22 @@ class AVIWriter:
         if self.frames:
             raise ValueError('set_audio comes before the first frame')
         self._audio = np.ascontiguousarray(samples, '<i2').reshape(-1)
+        self._audio_off, self._streamed = 0, False
+
+    def add_audio(self, samples):
+        """Appends int16 samples (pcm16 output) to the track, at any time before close(): the
+        streaming form of set_audio.  The sound must run ahead of the picture: write_frame raises
+        when a frame's share of the samples has not all arrived.  Samples already written out are
+        dropped, so a long stream holds only what is ahead of the picture."""
+        if self.audio_rate is None:
+            raise ValueError('the writer was opened without audio_rate')
+        if self._closed:
+            raise ValueError('the file is closed')
+        new = np.ascontiguousarray(samples, '<i2').reshape(-1)
+        used = max(0, min(self._share(self.frames) - self._audio_off, len(self._audio))) if self._streamed else 0
+        self._audio = np.concatenate([self._audio[used:], new])
+        self._audio_off += used
+        self._streamed = True
 
     def _share(self, i):
         return i * self.audio_rate * self.scale // self.rate
@@ -119,7 +138,12 @@ class AVIWriter:
         size = sum(len(p) for p in pieces)
         chunks, sound = 8 + size + (size & 1), b''
         if self.audio_rate is not None:
-            sound = self._audio[self._share(self.frames):self._share(self.frames + 1)].tobytes()
+            lo, hi = self._share(self.frames) - self._audio_off, self._share(self.frames + 1) - self._audio_off
+            if self._streamed and hi > len(self._audio):
+                raise ValueError(f'frame {self.frames} takes samples up to {hi + self._audio_off}, but only '
+                                 f'{len(self._audio) + self._audio_off} have been added: add_audio runs ahead '
+                                 f'of the frames')
+            sound = self._audio[lo:hi].tobytes()
             chunks += 8 + len(sound)
         entries = len(self._index) + (1 if self.audio_rate is None else 2)
         if self._size + chunks + 8 + 16 * entries > LIMIT:

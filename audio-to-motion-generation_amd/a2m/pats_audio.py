@@ -20,6 +20,9 @@
   log_mel_512_windows(wave, sr, starts, window=382, interval=6, mean=None, std=None, ...)
       == gather_windows(log_mel_512(wave, sr), starts, window, interval, mean, std), computing
       only the frames the gather reads (every `interval`-th of each window).
+  ResampleStream(orig_sr, target_sr, ...) / MelWindowStream(sr, overlap, time, ...)
+      resample and log_mel_512_windows (over inference.track_starts) for a signal that arrives in
+      pieces: push(samples), close(); the pieces concatenate to the offline result bit for bit.
 
 `y` may be a 1-D numpy array (returns numpy [F, M], as the reference does) or a device tensor
 [S] / [C, S] with contiguous samples (rows may be strided; returns [F, M] / [C, F, M]).
@@ -284,3 +287,249 @@ def log_mel_512_windows(wave, sr, starts, window=382, interval=6, mean=None, std
         mean, std = mean.contiguous(), std.contiguous()
     _launch(w2, plan, True, pad, eps, ids, n * nj, mean, std, out)
     return out
+
+
+# ------------------------------------------------------------------------------ streaming
+# The stateful forms of resample and log_mel_512_windows for audio that arrives in pieces
+# (DESIGN.md, Streaming inference).  Each stage keeps a linear sliding device buffer that holds
+# samples [base, base + len) of the signal, allocated once: capacity 2 * (largest live span) +
+# max_chunk, so that when a chunk no longer fits, the live samples move to the front in one
+# non-overlapping device copy.  What a push returns follows from sample counts on the host; nothing
+# is read back from the device.
+def _as_chunk(samples, device):
+    """[s] samples (device tensor, host tensor or numpy) -> a float32 tensor; host data stays on
+    the host (the copy into the buffer is the transfer)."""
+    if torch.is_tensor(samples):
+        x = samples.detach()
+        if x.is_cuda and x.device != device:
+            raise ValueError(f'samples are on {x.device}, the stream on {device}')
+    else:
+        x = torch.as_tensor(np.asarray(samples, dtype=np.float32))
+    if x.dim() != 1:
+        raise ValueError(f'a chunk is [s] samples of one channel, got {tuple(x.shape)}')
+    return x if x.dtype == torch.float32 else x.float()
+
+
+class _SlidingBuffer:
+    """Samples [base, base + len) of an unbounded signal in one device allocation."""
+
+    def __init__(self, live_max, max_chunk, device, align=1):
+        if max_chunk < 1:
+            raise ValueError('max_chunk must be >= 1')
+        self.live_max, self.max_chunk, self.align = int(live_max), int(max_chunk), int(align)
+        # `align` more: the kept span starts at a multiple of it, at most align - 1 below the need
+        self.cap = 2 * (self.live_max + self.align) + self.max_chunk
+        self.buf = torch.zeros(self.cap, device=device, dtype=torch.float32)
+        self.base, self.len = 0, 0
+
+    @property
+    def seen(self):
+        return self.base + self.len
+
+    def append(self, chunk, keep_from):
+        """Add chunk (<= max_chunk samples); samples below keep_from are no longer needed."""
+        s = chunk.shape[0]
+        assert s <= self.max_chunk
+        if self.len + s > self.cap:
+            lo = max(self.base, keep_from // self.align * self.align)
+            live = self.seen - lo
+            a = lo - self.base
+            assert live <= a and live + s <= self.cap, (live, a, s, self.cap)   # sized so by construction
+            if live:
+                self.buf[:live].copy_(self.buf[a:a + live])
+            self.base, self.len = lo, live
+        if s:
+            self.buf[self.len:self.len + s].copy_(chunk, non_blocking=True)
+        self.len += s
+
+
+class ResampleStream:
+    """resample() for a signal that arrives in pieces: the concatenation of every push() and of
+    close() equals resample(whole signal) bit for bit, whatever the chunking.
+
+    push(samples [s]) -> [r] (device): exactly the outputs whose whole tap support has arrived
+    (n_t + L <= seen - 1); close() -> [r]: the rest, up to ceil(S * target_sr / orig_sr), with zeros
+    past the end.  Equal rates pass the samples through.  A push larger than max_chunk is split
+    internally; after close(), push raises."""
+
+    def __init__(self, orig_sr, target_sr, res_type='kaiser_best', max_chunk=16384, device='cuda'):
+        self.cfg = _resample_cfg(orig_sr, target_sr, res_type)
+        self.device = torch.device(device if str(device) != 'cuda' else f'cuda:{torch.cuda.current_device()}')
+        self.samples_in, self.samples_out, self.closed = 0, 0, False
+        self.passthrough = self.cfg[0] == self.cfg[1]
+        self.max_chunk = int(max_chunk)
+        if self.max_chunk < 1:
+            raise ValueError('max_chunk must be >= 1')
+        if self.passthrough:
+            return
+        self.plan = ResamplePlan.get(self.device, *self.cfg)
+        self.P, self.Q, self.L, _ = self.plan.bank()
+        # after a push every ready output is out, so the next one's support [n_t - L + 1, n_t + L]
+        # is not complete: fewer than 2 L samples are live
+        self.sb = _SlidingBuffer(2 * self.L + 1, self.max_chunk, self.device)
+
+    def ready(self, seen, closed=False):
+        """Outputs [0, ready) are computable from `seen` samples (host arithmetic only)."""
+        if closed:
+            return resample_num_samples(seen, self.cfg[0], self.cfg[1])
+        x = seen - 1 - self.L          # n_t = t P div Q <= x
+        return 0 if x < 0 else ((x + 1) * self.Q - 1) // self.P + 1
+
+    def _keep_from(self):
+        return max(0, self.samples_out * self.P // self.Q - self.L + 1)
+
+    def _launch(self, out, t_begin, n_out, n_total):
+        sb = self.sb
+        N.check(N.lib.a2m_resample_stream_f32(F._p(sb.buf), sb.base, sb.len, n_total, self.cfg[0], self.cfg[1],
+                                              self.cfg[2], F._p(self.plan.dev), t_begin, n_out, F._p(out),
+                                              F._stream()), value_error=True)
+
+    def push(self, samples):
+        if self.closed:
+            raise ValueError('the stream is closed')
+        x = _as_chunk(samples, self.device)
+        if self.passthrough:
+            self.samples_in += x.shape[0]
+            self.samples_out += x.shape[0]
+            return x.to(self.device)
+        total = self.ready(self.samples_in + x.shape[0]) - self.samples_out
+        out = torch.empty(total, device=self.device, dtype=torch.float32)
+        done = 0
+        with torch.cuda.device(self.device):
+            for i in range(0, x.shape[0], self.max_chunk):
+                chunk = x[i:i + self.max_chunk]
+                self.sb.append(chunk, self._keep_from())
+                self.samples_in += chunk.shape[0]
+                n = self.ready(self.samples_in) - self.samples_out
+                self._launch(out[done:done + n], self.samples_out, n, -1)
+                self.samples_out += n
+                done += n
+        return out
+
+    def close(self):
+        if self.closed:
+            raise ValueError('the stream is closed')
+        self.closed = True
+        if self.passthrough:
+            return torch.empty(0, device=self.device, dtype=torch.float32)
+        n = self.ready(self.samples_in, True) - self.samples_out
+        out = torch.empty(n, device=self.device, dtype=torch.float32)
+        with torch.cuda.device(self.device):
+            self._launch(out, self.samples_out, n, self.samples_in)
+        self.samples_out += n
+        return out
+
+
+def mel_window_geometry(time=4.3, fs_new=15):
+    """(window, interval, T) of the audio/log_mel_512 windows, as inference.track_starts."""
+    from .windowing import window_index
+    _, window, interval = window_index(0, 'audio/log_mel_512', fs_new, time)
+    return window, interval, (window + interval - 1) // interval
+
+
+def mel_windows_due(seen, closed, window, interval, overlap, n_fft=2048, hop=512):
+    """How many windows [0, due) of a stream are computable once `seen` samples have arrived: the
+    pure host rule of MelWindowStream.  Window k starts at feature frame s_k = k (T - overlap)
+    interval and reads frames s_k + interval j, j < T.  While the stream is open it is due when
+    the frames seen so far hold it, num_frames(seen) >= s_k + window (the offline fit test, so no
+    window is emitted that the whole recording would not have), and its last frame is complete,
+    seen >= hop (s_k + interval (T - 1)) + n_fft / 2.  At close every window that fits the final
+    length is due; the frames that then reach past the end are reflected about it."""
+    T = (window + interval - 1) // interval
+    step = (T - overlap) * interval
+    nf = num_frames(seen, n_fft, hop, True) if seen > 0 else 0
+    fit = (nf - window) // step + 1 if nf >= window else 0
+    if closed:
+        return fit
+    room = seen - n_fft // 2 - hop * interval * (T - 1)
+    return min(fit, room // (hop * step) + 1) if room >= 0 else 0
+
+
+class MelWindowStream:
+    """log_mel_512_windows over inference.track_starts for a signal that arrives in pieces: the
+    concatenation of every push() and of close() equals
+    log_mel_512_windows(whole, sr, track_starts(num_frames(S), overlap, time, fs_new)[0], ...) bit
+    for bit, whatever the chunking.
+
+    push(samples [s]) -> [m, T, n_mels] (device), the windows that became due (mel_windows_due);
+    close() -> [m, T, n_mels], the windows that fit only the final length, with end reflection.
+    Mel rows shared by overlapping windows are recomputed.  After close(), push raises."""
+    N_FFT, HOP = 2048, 512
+
+    def __init__(self, sr, overlap=16, time=4.3, fs_new=15, mean=None, std=None, eps=1e-10,
+                 pad_mode='reflect', n_mels=128, max_chunk=16384, device='cuda'):
+        self.device = torch.device(device if str(device) != 'cuda' else f'cuda:{torch.cuda.current_device()}')
+        self.window, self.interval, self.T = mel_window_geometry(time, fs_new)
+        if not 0 <= overlap <= self.T // 2:
+            raise ValueError(f'overlap {overlap} outside [0, T/2 = {self.T // 2}]')
+        if pad_mode not in PAD_MODES:
+            raise ValueError(f"pad_mode must be 'reflect' or 'constant', got {pad_mode!r}")
+        if (mean is None) != (std is None):
+            raise ValueError('mean and std come together')
+        self.overlap, self.eps, self.pad_mode, self.pad = int(overlap), float(eps), pad_mode, PAD_MODES[pad_mode]
+        self.step = (self.T - self.overlap) * self.interval
+        self.plan = PatsAudioPlan.get(self.device, *_cfg_512(sr, n_mels))
+        self.mean = None if mean is None else mean.to(self.device, torch.float32).contiguous()
+        self.std = None if std is None else std.to(self.device, torch.float32).contiguous()
+        self.max_chunk = int(max_chunk)
+        hop, half = self.HOP, self.N_FFT // 2
+        # the next window is not yet due: fewer samples than the later of its two conditions asks
+        # for are live, counted from its first sample hop s_k - n_fft / 2
+        live = max(hop * self.interval * (self.T - 1) + 2 * half, hop * self.window + half) + hop
+        # the buffer is only ever compacted by multiples of the hop: the kernel's frame loads are
+        # vector loads from base-relative offsets (a2m_pats_audio_stream_f32)
+        self.sb = _SlidingBuffer(live, self.max_chunk, self.device, align=hop)
+        self.per_call = self.max_chunk // (hop * self.step) + 3      # windows one chunk can make due
+        k = torch.arange(self.per_call, device=self.device, dtype=torch.int64)
+        j = torch.arange(self.T, device=self.device, dtype=torch.int64)
+        self._rel = (k[:, None] * self.step + j[None, :] * self.interval).contiguous()
+        self._ids = torch.empty_like(self._rel)
+        self.samples_in, self.windows_out, self.closed = 0, 0, False
+
+    def due(self, seen, closed=False):
+        return mel_windows_due(seen, closed, self.window, self.interval, self.overlap, self.N_FFT, self.HOP)
+
+    def _keep_from(self):
+        return max(0, self.HOP * self.windows_out * self.step - self.N_FFT // 2)
+
+    def _emit(self, out, n, n_total):
+        """Windows [windows_out, windows_out + n) into out [n, T, n_mels]."""
+        sb, p = self.sb, self.plan
+        for i in range(0, n, self.per_call):
+            m = min(self.per_call, n - i)
+            torch.add(self._rel[:m], (self.windows_out + i) * self.step, out=self._ids[:m])
+            N.check(N.lib.a2m_pats_audio_stream_f32(F._p(sb.buf), sb.base, sb.len, n_total, p.n_fft, p.hop,
+                                                    p.win_length, p.n_mels, p.power, F._p(p.dev), 1, self.pad,
+                                                    self.eps, F._p(self._ids), m * self.T, F._p(self.mean),
+                                                    F._p(self.std), F._p(out[i:i + m]), F._stream()),
+                    value_error=True)
+        self.windows_out += n
+
+    def push(self, samples):
+        if self.closed:
+            raise ValueError('the stream is closed')
+        x = _as_chunk(samples, self.device)
+        total = self.due(self.samples_in + x.shape[0]) - self.windows_out
+        out = torch.empty(total, self.T, self.plan.n_mels, device=self.device, dtype=torch.float32)
+        done = 0
+        with torch.cuda.device(self.device):
+            for i in range(0, x.shape[0], self.max_chunk):
+                chunk = x[i:i + self.max_chunk]
+                self.sb.append(chunk, self._keep_from())
+                self.samples_in += chunk.shape[0]
+                n = self.due(self.samples_in) - self.windows_out
+                self._emit(out[done:done + n], n, -1)
+                done += n
+        return out
+
+    def close(self):
+        if self.closed:
+            raise ValueError('the stream is closed')
+        self.closed = True
+        n = self.due(self.samples_in, True) - self.windows_out
+        out = torch.empty(n, self.T, self.plan.n_mels, device=self.device, dtype=torch.float32)
+        if n:
+            _pad_mode(self.pad_mode, self.samples_in, self.N_FFT)
+            with torch.cuda.device(self.device):
+                self._emit(out, n, self.samples_in)
+        return out

@@ -145,19 +145,25 @@ struct PatsArgs {
   float log_eps;             // ln(eps) rounded once on the host: the value of a masked zero
   const float* mean;         // optional standardisation of the output, as a2m_window_gather_f32
   const float* std_;
+  // a2m_pats_audio_stream_f32 only (slide == 0 and base == 0 otherwise): `wave` is a sliding buffer
+  // that holds samples [base, base + len) of one signal, the ids are that signal's frame indices,
+  // and n_samples is its length once known (PATS_OPEN_END until then: no sample is past the end)
+  int slide;
+  int64_t base, len;
 };
+constexpr int64_t PATS_OPEN_END = (int64_t)1 << 62;
 
 // Sample p of the padded clip for p outside [0, S): only frames that touch a pad come here.
 // Reflection needs pad < S (host check), so one mirror lands inside; the clamp keeps a bad
-// caller in bounds.
+// caller in bounds.  clip points at sample `base` of the signal (0 for a whole clip).
 __device__ __forceinline__ float edge_sample(const float* __restrict__ clip, int64_t p, int64_t S,
-                                             bool pad_zero) {
+                                             bool pad_zero, int64_t base) {
   if (p < 0 || p >= S) {
     if (pad_zero) return 0.f;
     p = p < 0 ? -p : 2 * (S - 1) - p;
     p = p < 0 ? 0 : p >= S ? S - 1 : p;
   }
-  return clip[p];
+  return clip[p - base];
 }
 
 // Where output row `row` reads: its clip, the padded-clip index of its first sample, whether all
@@ -166,12 +172,35 @@ struct FrameSrc {
   const float* clip;
   int64_t start;
   bool interior, valid;
+  bool pad_zero;  // what edge_sample gives outside the signal (a frame that must not read: zeros)
 };
 __device__ __forceinline__ FrameSrc pats_frame(const float* __restrict__ wave, int64_t clip_stride,
                                                int n_frames, int hop, int nfft, int64_t row,
                                                const PatsArgs& pa) {
   int64_t id = pa.frame_ids ? pa.frame_ids[row] : row;
   FrameSrc f;
+  f.pad_zero = pa.pad_zero;
+  if (pa.slide) {
+    // The frame's samples, mirrors included (edge_sample), span one interval of the signal; what
+    // of it is not a defined zero must be in the buffer, else the row is NaN and nothing is read
+    // (the frame is moved wholly ahead of sample 0 and padded with zeros).
+    const int64_t S = pa.n_samples;
+    f.clip = wave;
+    f.valid = id >= 0 && id < pa.n_src;
+    const int64_t lo = (f.valid ? id : 0) * hop - pa.pad, hi = lo + nfft - 1;
+    int64_t need_lo = lo, need_hi = hi;
+    if (!pa.pad_zero) {
+      if (lo < 0 && -lo > need_hi) need_hi = -lo;
+      if (hi >= S && 2 * (S - 1) - hi < need_lo) need_lo = 2 * (S - 1) - hi;
+    }
+    need_lo = need_lo < 0 ? 0 : need_lo;
+    need_hi = need_hi >= S ? S - 1 : need_hi;
+    f.valid = f.valid && (need_lo > need_hi || (need_lo >= pa.base && need_hi < pa.base + pa.len));
+    f.start = f.valid ? lo : -(int64_t)nfft;
+    f.interior = f.valid && lo >= 0 && hi < S;
+    f.pad_zero = pa.pad_zero || !f.valid;
+    return f;
+  }
   f.valid = id >= 0 && id < pa.n_src;
   const uint32_t id32 = f.valid ? (uint32_t)id : 0u;  // n_src < 2^31 (host check)
   const uint32_t clip = id32 / (uint32_t)n_frames;
@@ -228,8 +257,8 @@ __global__ __launch_bounds__(256) void logmel_kernel(const float* __restrict__ w
     if (PATS) {  // the frame spans fft_len samples, the window sits at [lead, lead + win)
       const int wn = n - pa.lead;
       const bool in = wn >= 0 && wn < win && n < nfft;
-      sv[j] = !in ? 0.f : fs.interior ? fs.clip[fs.start + n]
-                                      : edge_sample(fs.clip, fs.start + n, pa.n_samples, pa.pad_zero);
+      sv[j] = !in ? 0.f : fs.interior ? fs.clip[fs.start - pa.base + n]
+                                      : edge_sample(fs.clip, fs.start + n, pa.n_samples, fs.pad_zero, pa.base);
       wv[j] = in ? window[wn] : 0.f;
       continue;
     }
@@ -476,7 +505,7 @@ __global__ __launch_bounds__(64 * LM_WAVES) void logmel2048_kernel(
   if (PATS) {  // read once per wave: the row index is wave-uniform
     const int row = __builtin_amdgcn_readfirstlane(active ? gframe : 0);
     fs = pats_frame(wave, clip_stride, n_frames, hop, 2 * M, row, pa);
-    src = fs.clip + fs.start;  // dereferenced by interior frames only
+    src = fs.clip + (fs.start - pa.base);  // dereferenced by interior frames only
   }
   f2* sx = s_region[wv];
 
@@ -505,8 +534,8 @@ __global__ __launch_bounds__(64 * LM_WAVES) void logmel2048_kernel(
 #pragma unroll
       for (int j = 0; j < 16; ++j) {
         const int64_t p = fs.start + 2 * (lane + 64 * j);
-        x[j] = (f2){edge_sample(fs.clip, p, pa.n_samples, pa.pad_zero),
-                    edge_sample(fs.clip, p + 1, pa.n_samples, pa.pad_zero)};
+        x[j] = (f2){edge_sample(fs.clip, p, pa.n_samples, fs.pad_zero, pa.base),
+                    edge_sample(fs.clip, p + 1, pa.n_samples, fs.pad_zero, pa.base)};
       }
     }
 #pragma unroll
@@ -902,6 +931,25 @@ int64_t a2m_pats_audio_num_frames(int64_t n_samples, int32_t n_fft, int32_t hop,
   return padded < n_fft ? 0 : 1 + (padded - n_fft) / hop;
 }
 
+// the launch both PATS entries end in: `total` output rows, nf frames per clip
+static int pats_launch(const float* wave, int64_t clip_stride, int64_t nf, int64_t total, int32_t n_fft,
+                       int32_t win_length, int32_t n_mels, const void* dev_plan, float eps, float* out,
+                       const PatsArgs& pa, void* stream) {
+  const unsigned char* plan = static_cast<const unsigned char*>(dev_plan);
+  if (n_fft == 2048 && win_length == 2048 && n_mels <= 128) {  // register FFT, one wave per frame
+    hipLaunchKernelGGL((logmel2048_kernel<true, true>), dim3((unsigned)cdiv(total, LM_WAVES)),
+                       dim3(64 * LM_WAVES), 0, as_stream(stream), wave, clip_stride, (int)nf,
+                       (int)total, plan, eps, out, pa);
+    A2M_LAUNCH_CHECK();
+    return A2M_OK;
+  }
+  const size_t lds = sizeof(float) * (2 * (size_t)n_fft + n_fft / 2 + 1 + 3);
+  hipLaunchKernelGGL(logmel_kernel<true>, dim3((unsigned)total), dim3(256), lds, as_stream(stream),
+                     wave, clip_stride, (int)nf, plan, eps, out, pa);
+  A2M_LAUNCH_CHECK();
+  return A2M_OK;
+}
+
 int a2m_pats_audio_f32(const float* wave, int64_t n_clips, int64_t clip_stride, int64_t n_samples,
                        int32_t n_fft, int32_t hop, int32_t win_length, int32_t n_mels, int32_t power,
                        const void* dev_plan, int32_t center, int32_t pad_mode, float eps,
@@ -938,19 +986,51 @@ int a2m_pats_audio_f32(const float* wave, int64_t n_clips, int64_t clip_stride, 
   pa.log_eps = (float)std::log((double)eps);
   pa.mean = mean;
   pa.std_ = std_;
-  const unsigned char* plan = static_cast<const unsigned char*>(dev_plan);
-  if (n_fft == 2048 && win_length == 2048 && n_mels <= 128) {  // register FFT, one wave per frame
-    hipLaunchKernelGGL((logmel2048_kernel<true, true>), dim3((unsigned)cdiv(total, LM_WAVES)),
-                       dim3(64 * LM_WAVES), 0, as_stream(stream), wave, clip_stride, (int)nf,
-                       (int)total, plan, eps, out, pa);
-    A2M_LAUNCH_CHECK();
-    return A2M_OK;
-  }
-  const size_t lds = sizeof(float) * (2 * (size_t)n_fft + n_fft / 2 + 1 + 3);
-  hipLaunchKernelGGL(logmel_kernel<true>, dim3((unsigned)total), dim3(256), lds, as_stream(stream),
-                     wave, clip_stride, (int)nf, plan, eps, out, pa);
-  A2M_LAUNCH_CHECK();
-  return A2M_OK;
+  return pats_launch(wave, clip_stride, nf, total, n_fft, win_length, n_mels, dev_plan, eps, out, pa, stream);
+}
+
+int a2m_pats_audio_stream_f32(const float* buf, int64_t base, int64_t len, int64_t n_total, int32_t n_fft,
+                              int32_t hop, int32_t win_length, int32_t n_mels, int32_t power,
+                              const void* dev_plan, int32_t center, int32_t pad_mode, float eps,
+                              const int64_t* frame_ids, int64_t n_out, const float* mean,
+                              const float* std_, float* out, void* stream) {
+  A2M_CHECK_ARG(n_fft >= 4 && n_fft <= 4096 && (n_fft & (n_fft - 1)) == 0 && hop > 0 &&
+                    win_length >= 2 && win_length <= n_fft,
+                "pats_audio_stream: bad geometry n_fft=%d hop=%d win_length=%d", n_fft, hop, win_length);
+  A2M_CHECK_ARG(power == 1 || power == 2, "pats_audio_stream: power %d must be 1 or 2", power);
+  A2M_CHECK_ARG(pad_mode == A2M_PAD_REFLECT || pad_mode == A2M_PAD_CONSTANT,
+                "pats_audio_stream: pad_mode %d is neither reflect nor constant", pad_mode);
+  A2M_CHECK_ARG(base >= 0 && len >= 0 && n_out >= 0 && n_mels > 0,
+                "pats_audio_stream: bad sizes (base %lld len %lld n_out %lld n_mels %d)", (long long)base,
+                (long long)len, (long long)n_out, n_mels);
+  A2M_CHECK_ARG(base <= PATS_OPEN_END - len && n_total < PATS_OPEN_END, "pats_audio_stream: sample index beyond 62 bits");
+  A2M_CHECK_ARG(base % 4 == 0 && (reinterpret_cast<uintptr_t>(buf) & 15) == 0,
+                "pats_audio_stream: base %lld must be a multiple of 4 samples and buf 16-byte aligned (the "
+                "frame loads are vector loads)", (long long)base);
+  A2M_CHECK_ARG(eps > 0.f, "pats_audio_stream: eps %g must be positive", (double)eps);
+  A2M_CHECK_ARG((mean == nullptr) == (std_ == nullptr), "pats_audio_stream: mean and std come together");
+  A2M_CHECK_ARG(!center || pad_mode != A2M_PAD_REFLECT || n_total < 0 || n_total > n_fft / 2,
+                "pats_audio_stream: reflect padding needs more than n_fft / 2 = %d samples, got %lld",
+                n_fft / 2, (long long)n_total);
+  if (n_out == 0) return A2M_OK;
+  A2M_CHECK_ARG(buf && out && dev_plan && frame_ids, "pats_audio_stream: null pointer");
+  A2M_CHECK_ARG(n_out < (1LL << 31), "pats_audio_stream: too many frames");
+  PatsArgs pa{};
+  pa.n_samples = n_total >= 0 ? n_total : PATS_OPEN_END;
+  pa.frame_ids = frame_ids;
+  // frames of the signal: all of them while the end is open (capped so that id * hop fits 62 bits)
+  pa.n_src = n_total >= 0 ? a2m_pats_audio_num_frames(n_total, n_fft, hop, center) : PATS_OPEN_END / hop;
+  pa.pad = center ? n_fft / 2 : 0;
+  pa.pad_zero = pad_mode == A2M_PAD_CONSTANT;
+  pa.lead = (n_fft - win_length) / 2;
+  pa.power = power;
+  pa.log_eps = (float)std::log((double)eps);
+  pa.mean = mean;
+  pa.std_ = std_;
+  pa.slide = 1;
+  pa.base = base;
+  pa.len = len;
+  return pats_launch(buf, 0, 1, n_out, n_fft, win_length, n_mels, dev_plan, eps, out, pa, stream);
 }
 
 }  // extern "C"

@@ -197,6 +197,27 @@ __global__ __launch_bounds__(256) void render_poses_kernel(
   }
 }
 
+// One element of the stitched track, shared by the offline and the streaming kernel: `val` is
+// channel c of frame j of its window, *prev (null outside an overlap) the same channel of frame
+// j + h of the window before.  The cross-fade is two rounded products and one rounded sum, written
+// out so that no context contracts it into an fma.
+__device__ __forceinline__ float track_blend_value(float val, const float* __restrict__ prev, int j,
+                                                   int overlap, int c, const float* __restrict__ mean,
+                                                   const float* __restrict__ std_) {
+  if (prev) {
+    const float w1 = __fdiv_rn(j + 0.5f, (float)overlap);
+    const float w0 = __fdiv_rn(overlap - j - 0.5f, (float)overlap);
+    val = __fadd_rn(__fmul_rn(w0, *prev), __fmul_rn(w1, val));
+  }
+  if (mean) {
+    // the two roundings of a2m_pose_denormalize_f32 (see pose_denormalize_kernel)
+    float scaled = val * std_[c];
+    asm volatile("" : "+v"(scaled));
+    val = scaled + mean[c];
+  }
+  return val;
+}
+
 // out frame f of the stitched track reads window k = min(f / h, n - 1) at j = f - k h, and, when
 // k > 0 and j < overlap, also window k - 1 at j + h; h = T - overlap.
 __global__ void track_blend_kernel(const float* __restrict__ win, int n, int T, int Fd, int overlap,
@@ -209,19 +230,51 @@ __global__ void track_blend_kernel(const float* __restrict__ win, int n, int T, 
     const int c = (int)(i - f * Fd);
     const int k = (int)min(f / h, (int64_t)n - 1);
     const int j = (int)(f - (int64_t)k * h);
-    float val = win[((int64_t)k * T + j) * Fd + c];
-    if (k > 0 && j < overlap) {
-      const float w1 = __fdiv_rn(j + 0.5f, (float)overlap);
-      const float w0 = __fdiv_rn(overlap - j - 0.5f, (float)overlap);
-      val = w0 * win[((int64_t)(k - 1) * T + j + h) * Fd + c] + w1 * val;
+    const float val = win[((int64_t)k * T + j) * Fd + c];
+    const float* prev = k > 0 && j < overlap ? win + ((int64_t)(k - 1) * T + j + h) * Fd + c : nullptr;
+    out[i] = track_blend_value(val, prev, j, overlap, c, mean, std_);
+  }
+}
+
+// The same track, m windows at a time.  `tail` [overlap][Fd] carries frames [h, T) of the last
+// window seen (normalised, as the generator gave them); has_prev says whether it holds one.  The
+// launch writes the m h frames that the new windows make final: frame f reads window k = f / h at
+// j = f - k h, and inside an overlap the window before, which for k = 0 is the tail.  Element
+// (j, c) of the tail is read and then rewritten by the one thread that owns output (j, c) of
+// window 0 (overlap <= h, so those outputs all belong to window 0): no ordering between threads
+// is needed.  With `flush`, the overlap frames after them are the (new) tail, unblended.
+__global__ void track_blend_stream_kernel(const float* __restrict__ win, int m, int T, int Fd, int overlap,
+                                          float* __restrict__ tail, int has_prev, int flush,
+                                          const float* __restrict__ mean, const float* __restrict__ std_,
+                                          int64_t total, float* __restrict__ out) {
+  const int h = T - overlap;
+  const int64_t body = (int64_t)m * h * Fd;
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < total;
+       i += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t f = i / Fd;
+    const int c = (int)(i - f * Fd);
+    if (i >= body) {  // flush: frame h + j of the last window
+      const int j = (int)(f - (int64_t)m * h);
+      const float val = m > 0 ? win[((int64_t)(m - 1) * T + h + j) * Fd + c] : tail[(int64_t)j * Fd + c];
+      out[i] = track_blend_value(val, nullptr, h + j, overlap, c, mean, std_);
+      continue;
     }
-    if (mean) {
-      // the two roundings of a2m_pose_denormalize_f32 (see pose_denormalize_kernel)
-      float scaled = val * std_[c];
-      asm volatile("" : "+v"(scaled));
-      val = scaled + mean[c];
+    const int k = (int)(f / h);
+    const int j = (int)(f - (int64_t)k * h);
+    const float val = win[((int64_t)k * T + j) * Fd + c];
+    const float* prev = nullptr;
+    float carried = 0.f;
+    if (j < overlap) {
+      if (k > 0) {
+        prev = win + ((int64_t)(k - 1) * T + j + h) * Fd + c;
+      } else {
+        float* slot = tail + (int64_t)j * Fd + c;
+        carried = *slot;
+        if (has_prev) prev = &carried;
+        *slot = win[((int64_t)(m - 1) * T + h + j) * Fd + c];
+      }
     }
-    out[i] = val;
+    out[i] = track_blend_value(val, prev, j, overlap, c, mean, std_);
   }
 }
 
@@ -293,6 +346,26 @@ int a2m_track_blend_f32(const float* win, int32_t n, int32_t T, int32_t Fd, int3
   const int blocks = (int)std::min<int64_t>(cdiv(total, 256), 4096);
   hipLaunchKernelGGL(track_blend_kernel, dim3(blocks), dim3(256), 0, as_stream(stream), win, n, T, Fd,
                      overlap, mean, std_, total, out);
+  A2M_LAUNCH_CHECK();
+  return A2M_OK;
+}
+
+int a2m_track_blend_stream_f32(const float* win, int32_t m, int32_t T, int32_t Fd, int32_t overlap,
+                               float* tail, int32_t has_prev, int32_t flush, const float* mean,
+                               const float* std_, float* out, void* stream) {
+  A2M_CHECK_ARG(m >= 0 && T >= 1 && Fd >= 1,
+                "track_blend_stream: need m >= 0, T >= 1, Fd >= 1 (m %d T %d Fd %d)", m, T, Fd);
+  A2M_CHECK_ARG(overlap >= 0 && overlap <= T / 2, "track_blend_stream: overlap %d outside [0, T/2 = %d]",
+                overlap, T / 2);
+  A2M_CHECK_ARG((mean == nullptr) == (std_ == nullptr), "track_blend_stream: mean and std come together");
+  A2M_CHECK_ARG(!flush || m > 0 || has_prev, "track_blend_stream: a flush with no window before it");
+  const int64_t total = ((int64_t)m * (T - overlap) + (flush ? overlap : 0)) * Fd;
+  if (m > 0 || flush) A2M_CHECK_ARG(tail || overlap == 0, "track_blend_stream: null tail");
+  if (total == 0) return A2M_OK;  // nothing final: no window, or a flush at overlap 0
+  A2M_CHECK_ARG((win || m == 0) && out, "track_blend_stream: null pointer");
+  const int blocks = (int)std::min<int64_t>(cdiv(total, 256), 4096);
+  hipLaunchKernelGGL(track_blend_stream_kernel, dim3(blocks), dim3(256), 0, as_stream(stream), win, m, T,
+                     Fd, overlap, tail, has_prev != 0, flush != 0, mean, std_, total, out);
   A2M_LAUNCH_CHECK();
   return A2M_OK;
 }

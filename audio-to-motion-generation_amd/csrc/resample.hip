@@ -126,40 +126,47 @@ static int resample_plan(int32_t sr_in, int32_t sr_out, int32_t num_zeros, doubl
 }
 
 // ------------------------------------------------------------------------------ device
-// Tile `blockIdx.x % tiles` of clip `blockIdx.x / tiles`.  STAGED: xs holds samples
-// [lo, lo + count) of the clip, count <= span_cap (the host sizes span_cap from the same
-// arithmetic, so the clamp never bites; it keeps LDS writes in bounds whatever the caller passed).
-template <int OPT, bool STAGED>
-__global__ __launch_bounds__(RS_THREADS) void resample_kernel(
-    const float* __restrict__ wave, int64_t clip_stride, int64_t n_samples,
-    const float* __restrict__ bankT, int P, int Q, int L, float* __restrict__ out, int64_t out_stride,
-    int64_t n_out, int tiles, int span_cap) {
-  extern __shared__ __attribute__((aligned(16))) float xs[];
-  const int64_t clip_id = blockIdx.x / (unsigned)tiles;
-  const int64_t t0 = (int64_t)(blockIdx.x % (unsigned)tiles) * (OPT * RS_THREADS);
-  const float* clip = wave + clip_id * clip_stride;
-  float* dst = out + clip_id * out_stride;
+// Where a sample comes from.  Both fetches return x[g] for the global sample index g of one
+// signal and 0 where the signal is defined to be zero; everything downstream of the fetch (the
+// staging, the tap loop, the fmaf chain) is resample_tile, shared by the offline and the
+// streaming kernel, so the two agree bit for bit.
+struct ClipFetch {   // a whole clip: x = 0 outside [0, n)
+  const float* __restrict__ clip;
+  int64_t n;
+  __device__ __forceinline__ float operator()(int64_t g) const { return g >= 0 && g < n ? clip[g] : 0.f; }
+};
+struct SlideFetch {  // a sliding buffer holding [base, base + len): x = 0 outside [lo, hi), which the
+  const float* __restrict__ buf;  // host has clipped to the buffer (a2m_resample_stream_f32)
+  int64_t base, lo, hi;
+  __device__ __forceinline__ float operator()(int64_t g) const { return g >= lo && g < hi ? buf[g - base] : 0.f; }
+};
+
+// Outputs [t0, min(t0 + OPT * RS_THREADS, t_end)) of one signal, written to dst[t - t_org].
+// STAGED: xs holds samples [lo, lo + count) of the signal, count <= span_cap (the host sizes
+// span_cap from the same arithmetic, so the clamp never bites; it keeps LDS writes in bounds
+// whatever the caller passed).
+template <int OPT, bool STAGED, class Fetch>
+__device__ __forceinline__ void resample_tile(const Fetch& fetch, const float* __restrict__ bankT, int P,
+                                              int Q, int L, float* __restrict__ dst, int64_t t0,
+                                              int64_t t_end, int64_t t_org, int span_cap, float* xs) {
   int64_t lo = 0;
   if (STAGED) {
-    const int64_t t_last = (t0 + OPT * RS_THREADS < n_out ? t0 + OPT * RS_THREADS : n_out) - 1;
+    const int64_t t_last = (t0 + OPT * RS_THREADS < t_end ? t0 + OPT * RS_THREADS : t_end) - 1;
     lo = t0 * P / Q - L + 1;
     const int64_t span = t_last * P / Q + L - lo + 1;
     const int count = (int)(span < span_cap ? span : span_cap);
 #pragma unroll 4
-    for (int i = threadIdx.x; i < count; i += RS_THREADS) {
-      const int64_t g = lo + i;
-      xs[i] = g >= 0 && g < n_samples ? clip[g] : 0.f;
-    }
+    for (int i = threadIdx.x; i < count; i += RS_THREADS) xs[i] = fetch(lo + i);
     __syncthreads();
   }
   float acc[OPT];
-  int64_t first[OPT];  // clip index of the output's tap 0 (k = -L + 1)
+  int64_t first[OPT];  // signal index of the output's tap 0 (k = -L + 1)
   int off[OPT], row[OPT];
   bool live[OPT];
 #pragma unroll
   for (int i = 0; i < OPT; ++i) {
     const int64_t t = t0 + threadIdx.x + i * RS_THREADS;
-    live[i] = t < n_out;
+    live[i] = t < t_end;
     const int64_t tt = live[i] ? t : t0;  // a thread past the end repeats the tile's first output
     first[i] = tt * P / Q - L + 1;
     off[i] = (int)(first[i] - lo);
@@ -172,19 +179,36 @@ __global__ __launch_bounds__(RS_THREADS) void resample_kernel(
     const float* hj = bankT + j * Q;  // 2 L Q <= RS_MAX_BANK
 #pragma unroll
     for (int i = 0; i < OPT; ++i) {
-      float x;
-      if (STAGED) {
-        x = xs[off[i] + j];
-      } else {
-        const int64_t g = first[i] + j;
-        x = g >= 0 && g < n_samples ? clip[g] : 0.f;
-      }
+      const float x = STAGED ? xs[off[i] + j] : fetch(first[i] + j);
       acc[i] = fmaf(hj[row[i]], x, acc[i]);
     }
   }
 #pragma unroll
   for (int i = 0; i < OPT; ++i)
-    if (live[i]) dst[t0 + threadIdx.x + i * RS_THREADS] = acc[i];
+    if (live[i]) dst[t0 + threadIdx.x + i * RS_THREADS - t_org] = acc[i];
+}
+
+// Tile `blockIdx.x % tiles` of clip `blockIdx.x / tiles`.
+template <int OPT, bool STAGED>
+__global__ __launch_bounds__(RS_THREADS) void resample_kernel(
+    const float* __restrict__ wave, int64_t clip_stride, int64_t n_samples,
+    const float* __restrict__ bankT, int P, int Q, int L, float* __restrict__ out, int64_t out_stride,
+    int64_t n_out, int tiles, int span_cap) {
+  extern __shared__ __attribute__((aligned(16))) float xs[];
+  const int64_t clip_id = blockIdx.x / (unsigned)tiles;
+  const int64_t t0 = (int64_t)(blockIdx.x % (unsigned)tiles) * (OPT * RS_THREADS);
+  const ClipFetch fetch{wave + clip_id * clip_stride, n_samples};
+  resample_tile<OPT, STAGED>(fetch, bankT, P, Q, L, out + clip_id * out_stride, t0, n_out, 0, span_cap, xs);
+}
+
+// Tile blockIdx.x of the outputs [t_begin, t_end) of one unbounded signal, out[t - t_begin].
+template <int OPT, bool STAGED>
+__global__ __launch_bounds__(RS_THREADS) void resample_stream_kernel(
+    SlideFetch fetch, const float* __restrict__ bankT, int P, int Q, int L, float* __restrict__ out,
+    int64_t t_begin, int64_t t_end, int span_cap) {
+  extern __shared__ __attribute__((aligned(16))) float xs[];
+  const int64_t t0 = t_begin + (int64_t)blockIdx.x * (OPT * RS_THREADS);
+  resample_tile<OPT, STAGED>(fetch, bankT, P, Q, L, out, t0, t_end, t_begin, span_cap, xs);
 }
 
 }  // namespace a2m
@@ -266,6 +290,55 @@ int a2m_resample_f32(const float* wave, int64_t n_clips, int64_t clip_stride, in
     hipLaunchKernelGGL((resample_kernel<1, false>), grid, dim3(RS_THREADS), 0, as_stream(stream), wave,
                        clip_stride, n_samples, bankT, (int)r.P, (int)r.Q, (int)r.L, out, out_stride, n_out,
                        (int)tiles, 0);
+  }
+  A2M_LAUNCH_CHECK();
+  return A2M_OK;
+}
+
+int a2m_resample_stream_f32(const float* buf, int64_t base, int64_t len, int64_t n_total, int32_t sr_in,
+                            int32_t sr_out, int32_t num_zeros, const void* dev_plan, int64_t t_begin,
+                            int64_t n_out, float* out, void* stream) {
+  A2M_CHECK_ARG(base >= 0 && len >= 0 && t_begin >= 0 && n_out >= 0,
+                "resample_stream: negative size (base %lld len %lld t_begin %lld n_out %lld)",
+                (long long)base, (long long)len, (long long)t_begin, (long long)n_out);
+  Ratio r;
+  const int rc = resample_ratio(sr_in, sr_out, num_zeros, &r);
+  if (rc) return rc;
+  const int64_t lim = ((int64_t)1 << 62) / std::max(r.P, r.Q);
+  A2M_CHECK_ARG(base <= lim - len && t_begin <= lim - n_out && n_total <= lim,
+                "resample_stream: sample or output indices times P or Q do not fit 62 bits");
+  if (n_out == 0) return A2M_OK;
+  A2M_CHECK_ARG(buf && out && dev_plan, "resample_stream: null pointer");
+  // samples the outputs [t_begin, t_begin + n_out) read: [need_lo, need_hi]; what of it is not a
+  // defined zero (g < 0, or g >= n_total once the end is known) must lie in the buffer
+  const int64_t t_end = t_begin + n_out;
+  const int64_t need_lo = std::max<int64_t>(t_begin * r.P / r.Q - r.L + 1, 0);
+  int64_t need_hi = (t_end - 1) * r.P / r.Q + r.L;
+  if (n_total >= 0) need_hi = std::min(need_hi, n_total - 1);
+  A2M_CHECK_ARG(need_lo > need_hi || (need_lo >= base && need_hi < base + len),
+                "resample_stream: outputs [%lld, %lld) read samples [%lld, %lld], the buffer holds "
+                "[%lld, %lld)",
+                (long long)t_begin, (long long)t_end, (long long)need_lo, (long long)need_hi,
+                (long long)base, (long long)(base + len));
+  SlideFetch fetch;
+  fetch.buf = buf;
+  fetch.base = base;
+  fetch.lo = base;  // base >= 0
+  fetch.hi = n_total >= 0 ? std::min(base + len, n_total) : base + len;
+  const float* bankT = reinterpret_cast<const float*>(static_cast<const unsigned char*>(dev_plan) +
+                                                      rs_align16(sizeof(ResampleHeader)));
+  const int64_t span = ((RS_TILE - 1) * r.P + r.Q - 1) / r.Q + 2 * r.L;  // as a2m_resample_f32
+  const bool staged = span <= RS_MAX_SPAN;
+  const int64_t tiles = cdiv(n_out, staged ? RS_TILE : RS_THREADS);
+  A2M_CHECK_ARG(tiles < (1LL << 31), "resample_stream: too many output tiles");
+  const dim3 grid((unsigned)tiles);
+  if (staged) {
+    hipLaunchKernelGGL((resample_stream_kernel<RS_OPT, true>), grid, dim3(RS_THREADS),
+                       sizeof(float) * (size_t)span, as_stream(stream), fetch, bankT, (int)r.P, (int)r.Q,
+                       (int)r.L, out, t_begin, t_end, (int)span);
+  } else {
+    hipLaunchKernelGGL((resample_stream_kernel<1, false>), grid, dim3(RS_THREADS), 0, as_stream(stream),
+                       fetch, bankT, (int)r.P, (int)r.Q, (int)r.L, out, t_begin, t_end, 0);
   }
   A2M_LAUNCH_CHECK();
   return A2M_OK;

@@ -92,6 +92,26 @@ int a2m_pats_audio_f32(const float* wave, int64_t n_clips, int64_t clip_stride, 
                        const void* dev_plan, int32_t center, int32_t pad_mode, float eps,
                        const int64_t* frame_ids, int64_t n_out, const float* mean, const float* std_,
                        float* out, void* stream);
+/* The same features of a signal that arrives in pieces.  buf is a linear sliding device buffer
+ * holding samples [base, base + len) of one unbounded signal (sample g at buf[g - base]);
+ * n_total is the signal's length once its end is known, negative until then.  frame_ids (device
+ * int64, required) are absolute frame indices of that signal: frame i spans samples
+ * [i hop - n_fft/2, i hop + n_fft/2) when centred.  Padding about sample 0 is as offline
+ * (reflection, or zeros under A2M_PAD_CONSTANT); about the end it applies only when n_total >= 0.
+ * A frame that needs a sample the buffer does not hold and that is not a defined zero (before
+ * `base`, not yet arrived, past an unknown end), or whose id lies outside the signal, gives a row
+ * of NaN and reads nothing.  The per-frame arithmetic is the offline kernel's own code, so a frame
+ * equals a2m_pats_audio_f32's of the whole signal bit for bit.  The frame loads are vector loads:
+ * base must be a multiple of 4 samples and buf 16-byte aligned (compact the buffer by multiples of
+ * the hop).  mean / std as above.  A2M_EINVAL: bad geometry, negative base / len / n_out, a
+ * misaligned base or buf, mean without std, reflect padding with 0 <= n_total <= n_fft/2, a null
+ * pointer with n_out > 0.  n_out = 0 returns A2M_OK.  No allocation, no host synchronisation:
+ * capturable. */
+int a2m_pats_audio_stream_f32(const float* buf, int64_t base, int64_t len, int64_t n_total, int32_t n_fft,
+                              int32_t hop, int32_t win_length, int32_t n_mels, int32_t power,
+                              const void* dev_plan, int32_t center, int32_t pad_mode, float eps,
+                              const int64_t* frame_ids, int64_t n_out, const float* mean,
+                              const float* std_, float* out, void* stream);
 
 /* ---------------------------------------------------------------- waveform resampling
  * What librosa.core.resample did ahead of log_mel_400 (pats/data_loading/audio.py:88): band-limited
@@ -125,6 +145,17 @@ int a2m_resample_plan_bank(const void* host_plan, size_t plan_bytes, int32_t* P,
 int a2m_resample_f32(const float* wave, int64_t n_clips, int64_t clip_stride, int64_t n_samples,
                      int32_t sr_in, int32_t sr_out, int32_t num_zeros, const void* dev_plan, float* out,
                      int64_t out_stride, int64_t n_out, void* stream);
+/* Outputs t in [t_begin, t_begin + n_out) of the same formula for a signal that arrives in pieces:
+ * out[t - t_begin] = y[t].  buf is a linear sliding device buffer holding samples [base, base + len)
+ * (sample g at buf[g - base]); x[g] = 0 for g < 0, and for g >= n_total once the end is known
+ * (n_total >= 0; negative: still open).  The tap loop is a2m_resample_f32's own code, so y[t]
+ * equals the offline result bit for bit.  Never reads outside [base, base + len).  A2M_EINVAL: a
+ * null pointer with n_out > 0, a negative base / len / t_begin / n_out, or an output whose taps
+ * reach a sample that the buffer does not hold and that is not a defined zero.  n_out = 0 returns
+ * A2M_OK.  No allocation, no host synchronisation: capturable. */
+int a2m_resample_stream_f32(const float* buf, int64_t base, int64_t len, int64_t n_total, int32_t sr_in,
+                            int32_t sr_out, int32_t num_zeros, const void* dev_plan, int64_t t_begin,
+                            int64_t n_out, float* out, void* stream);
 
 /* ---------------------------------------------------------------- convolutions
  * ConvNormRelu (model_layers.py:51-118) forward in eval mode: conv + bias, optional
@@ -906,6 +937,21 @@ int a2m_render_poses_u8(const float* kp, int32_t N, int32_t P, int32_t K, const 
  * range, one of mean / std alone, null win or out with n > 0.  n = 0 returns A2M_OK. */
 int a2m_track_blend_f32(const float* win, int32_t n, int32_t T, int32_t Fd, int32_t overlap,
                         const float* mean, const float* std_, float* out, void* stream);
+/* The same track, m >= 0 new consecutive windows win [m][T][Fd] at a time.  tail [overlap][Fd] is
+ * device state owned by the caller: frames [h, T) of the last window seen, normalised; has_prev
+ * says whether it holds one (0 at the start of a stream).  The call writes the m*h frames that the
+ * new windows make final to out (the first `overlap` of them cross-faded with the tail when
+ * has_prev), then rewrites the tail from window m - 1.  flush != 0 also writes, after them, the
+ * `overlap` tail frames of the last window unblended: the end of the stream; out is then
+ * [m*h + overlap][Fd].  Every element goes through a2m_track_blend_f32's own arithmetic, so the
+ * calls of a stream, concatenated, equal the offline track bit for bit.  No atomics; each tail
+ * element is read and rewritten by one thread.  A2M_EINVAL: T or Fd < 1, m < 0, overlap out of
+ * range, one of mean / std alone, a flush with m = 0 and no window before it, a null win, tail
+ * (overlap > 0) or out where it is needed.  m = 0 without flush returns A2M_OK.  No allocation, no
+ * host synchronisation: capturable. */
+int a2m_track_blend_stream_f32(const float* win, int32_t m, int32_t T, int32_t Fd, int32_t overlap,
+                               float* tail, int32_t has_prev, int32_t flush, const float* mean,
+                               const float* std_, float* out, void* stream);
 
 /* ---- Baseline JPEG of rendered frames (generate_motion_video.py:174-185 writes %04d.jpg) ----
  * a2m_jpeg_encode_u8 turns frames [N][3][H][W] (uint8 planes that already hold Y, Cb, Cr in full
