@@ -7,6 +7,8 @@ a2m.video renders pose tracks to frames and YUV4MPEG2 files, or through a2m.jpeg
 on the device) and a2m.avi to Motion-JPEG AVI with sound; a2m.inference.generate_track stitches a
 recording's windows into one track and generate_video writes it as such a file.
 a2m.data.PatsLoader keeps a speaker's intervals in HBM and forms each training batch in one launch.
+a2m.baselines holds the median-pose, random-clip and nearest-audio predictors that a2m.evaluation
+scores beside a generator.
 """
 import torch  # noqa: F401  (loads the ROCm runtime the library links against first)
 

@@ -175,6 +175,10 @@ SIGNATURES = {
     'a2m_pck_f32': (ctypes.c_int, [P, P, I32, I32, F64, P, P]),
     'a2m_window_gather_f32': (ctypes.c_int, [P, I64, I32, P, I32, I32, I32, P, P, P, P]),
     'a2m_batch_gather_f32': (ctypes.c_int, [I32, P, P, P, P, P, P, P, P, P, P, I64, I32, P]),
+    'a2m_nn_search_ws_bytes': (SZ, [I32, I64]),
+    'a2m_nn_search_f32': (ctypes.c_int, [P, P, I64, I64, I32, I32, I32, I32, P, P, P, I32, P, P, P, SZ, P]),
+    'a2m_window_median_ws_bytes': (SZ, [I32]),
+    'a2m_window_median_f32': (ctypes.c_int, [P, P, I64, I64, I32, I32, I32, I32, P, P, SZ, P]),
     'a2m_render_poses_u8': (ctypes.c_int, [P, I32, I32, I32, P, P, P, I32, P, F32, P, I32, I32, P, P]),
     'a2m_track_blend_f32': (ctypes.c_int, [P, I32, I32, I32, I32, P, P, P, P]),
     'a2m_jpeg_ws_bytes': (SZ, [I32, I32, I32]),

@@ -1316,6 +1316,64 @@ def eval_sync_finish(part, style, T, lag_sums, lag_n):
     return lag_sums, lag_n
 
 
+def _check_table(arena, start, lo, n, name):
+    """The arena [rows, C] and start table of a PatsLoader modality, and the table range [lo, lo + n)."""
+    _check_dev(arena)
+    _check_int(start, torch.int64, (start.numel(),), 'start')
+    if arena.dim() != 2 or not arena.is_contiguous():
+        raise ValueError(f'{name}: arena must be a contiguous [rows, C] tensor')
+    lo, n = int(lo), int(n)
+    if lo < 0 or n <= 0 or lo + n > start.numel():
+        raise ValueError(f'{name}: table range [{lo}, {lo + n}) outside the {start.numel()} entries of start')
+    return lo, n
+
+
+def nn_search(query, arena, start, lo, n_cand, window, interval, mean=None, std=None):
+    """Nearest window of the arena for every query (a2m_nn_search_f32): query [B, T, C]; the
+    candidates are the windows at table positions [lo, lo + n_cand) of start (int64, arena rows),
+    T = ceil(window / interval) rows of arena [rows, C] each, read in place.  With mean and std
+    ([C]) the candidates are standardised as the loader's gather standardises them.  Returns
+    (best int64 [B], absolute table positions, the lowest among equal distances; best_dist [B], the
+    squared distances).  No host synchronisation: the two launches capture into a graph."""
+    _check_dev(query, mean, std)
+    lo, n_cand = _check_table(arena, start, lo, n_cand, 'nn_search')
+    if (mean is None) != (std is None):
+        raise ValueError('nn_search: mean and std come together')
+    C = arena.shape[1]
+    T = (int(window) + int(interval) - 1) // int(interval) if window > 0 and interval > 0 else 0
+    if query.dim() != 3 or tuple(query.shape[1:]) != (T, C):
+        raise ValueError(f'nn_search: query must be [B, {T}, {C}], got {tuple(query.shape)}')
+    query = query.contiguous()
+    B = query.shape[0]
+    if mean is not None:
+        mean, std = mean.contiguous(), std.contiguous()
+        if mean.numel() != C or std.numel() != C:
+            raise ValueError(f'nn_search: mean and std must hold {C} values')
+    best = torch.empty(B, dtype=torch.int64, device=query.device)
+    best_dist = torch.empty(B, device=query.device)
+    need = N.lib.a2m_nn_search_ws_bytes(B, n_cand)
+    ws = torch.empty(max(need, 8), dtype=torch.uint8, device=query.device)
+    N.check(N.lib.a2m_nn_search_f32(_p(arena), _p(start), lo, n_cand, C, int(window), int(interval),
+                                    0 if mean is None else 1, _p(mean), _p(std), _p(query), B, _p(best),
+                                    _p(best_dist), _p(ws), ws.numel(), _stream()))
+    return best, best_dist
+
+
+def window_median(arena, start, lo, n, window, interval, necksub=False):
+    """Exact per-channel median (numpy.median's value) over every row of the windows at table
+    positions [lo, lo + n) of start (a2m_window_median_f32); a frame that overlapping windows share
+    counts once per window.  necksub=True (C = 104) takes the median of x[c] - x[neck].  Returns
+    [C].  No host synchronisation."""
+    lo, n = _check_table(arena, start, lo, n, 'window_median')
+    C = arena.shape[1]
+    out = torch.empty(C, device=arena.device)
+    need = N.lib.a2m_window_median_ws_bytes(C)
+    ws = torch.empty(max(need, 4), dtype=torch.uint8, device=arena.device)
+    N.check(N.lib.a2m_window_median_f32(_p(arena), _p(start), lo, n, C, int(window), int(interval),
+                                        2 if necksub else 0, _p(out), _p(ws), ws.numel(), _stream()))
+    return out
+
+
 def gather_segments_(dst, segments):
     """dst[off:off + t.numel()] = t.reshape(-1) for every (off, t) in segments (contiguous fp32
     device tensors), 48 segments per launch (a2m_gather_segments_f32)."""

@@ -894,6 +894,55 @@ int a2m_batch_gather_f32(int32_t n_mod, const float* const* arena, const int64_t
                          const int32_t* mode, const float* const* mean, const float* const* std_,
                          float* const* out, const int64_t* order, int64_t b0, int32_t n, void* stream);
 
+/* ---- Evaluation baselines over the loader's arena (a2m/baselines.py; csrc/baselines.hip) ----
+ * Both entries address windows exactly as a2m_batch_gather_f32 does: the window at table position p
+ * is the rows arena[start[p] + j*interval], j < T = ceil(window / interval), of an arena
+ * [rows][C] float32, C % 4 == 0, arena 16-byte aligned.  They read the arena through the start
+ * table in place: no [n][T*C] copy of the windows exists.  The kernels check no bounds: the caller
+ * guarantees start[lo .. lo+n) and start + window within the arena.  No host synchronisation; the
+ * launches (and one memset node of the median) capture into a HIP graph.
+ *
+ * a2m_nn_search_f32: for every query b < B (query [B][T][C], 16-byte aligned) and every table
+ * position p in [lo, lo + n_cand)
+ *   d(b,p) = sum_{j<T, c<C} (query[b][j][c] - f(arena[start[p] + j*interval][c]))^2
+ * with f the identity for A2M_BATCH_RAW (mean, std_ NULL) and the gather's
+ * (x - mean[c]) / (std[c] < 1e-7 ? 1 : std[c]) for A2M_BATCH_STANDARDISE (both given).  best[b]
+ * (int64) is the absolute position p of the smallest computed d, the lowest p among bitwise-equal
+ * values (so best serves as `order` with b0 = 0 of a2m_batch_gather_f32); best_dist[b] is that
+ * value, clamped at 0.  d is computed as (|q|^2 + |w|^2) - 2 q.w in fp32: q.w on the exact fp32
+ * MFMA as one k-ordered fma chain per (b, p), the two norms as fixed fma chains and a fixed
+ * 16-lane tree.  The computed d(b,p) is a function of the query's and the window's values alone
+ * (not of p's place in the table, a tile or a chunk), and the result does not depend on workgroup
+ * scheduling: every candidate chunk writes its own (distance bits, p) minimum per query into ws,
+ * and a second small launch takes the minimum over the chunks.  Error: |d - exact| <=
+ * 4 K 2^-24 (|q|^2 + |w|^2), K = T*C.  Inputs must be finite.  ws: a2m_nn_search_ws_bytes(B, n_cand)
+ * bytes, 8-byte aligned.
+ * A2M_EINVAL before any launch: a NULL arena, start, query, best, best_dist or ws; B, n_cand,
+ * window or interval <= 0; C <= 0 or C % 4; lo < 0; a mode other than RAW / STANDARDISE; mean /
+ * std_ not as the mode requires; arena, query, mean or std_ not 16-byte aligned; ws_bytes too small; n_cand > 2^31 - 2^16
+ * or T*C > 2^30 (32-bit candidate and k indices). */
+size_t a2m_nn_search_ws_bytes(int32_t B, int64_t n_cand);
+int a2m_nn_search_f32(const float* arena, const int64_t* start, int64_t lo, int64_t n_cand, int32_t C,
+                      int32_t window, int32_t interval, int32_t mode, const float* mean,
+                      const float* std_, const float* query, int32_t B, int64_t* best,
+                      float* best_dist, void* ws, size_t ws_bytes, void* stream);
+
+/* a2m_window_median_f32: out[c], c < C, is the exact median (numpy.median's value) of the multiset
+ * { g(row)[c] : row of window p, p in [lo, lo + n) }, M = n*T values; a frame shared by overlapping
+ * windows counts once per window.  g is the identity for A2M_BATCH_RAW and, for A2M_BATCH_NECKSUB
+ * (C == 104), x[c] - x[neck] (one fp32 subtraction), neck = column 0 for c < 52, else column 52.
+ * M odd: the middle element; M even: the two middle elements added in double, halved and rounded
+ * once to float.  Inputs must be finite.  A radix select on the order-preserving integer image of
+ * the float, 8 bits a pass, four passes, both ranks carried at once; the bucket of each pass is
+ * chosen on the device.  ws: a2m_window_median_ws_bytes(C) bytes, 4-byte aligned.
+ * A2M_EINVAL before any launch: a NULL arena, start, out or ws; n, window or interval <= 0; C <= 0,
+ * C % 4 or C > 2^20; lo < 0; a mode other than RAW / NECKSUB; NECKSUB with C != 104; a misaligned
+ * arena; ws_bytes too small; n*T >= 2^32 (32-bit ranks and counts). */
+size_t a2m_window_median_ws_bytes(int32_t C);
+int a2m_window_median_f32(const float* arena, const int64_t* start, int64_t lo, int64_t n, int32_t C,
+                          int32_t window, int32_t interval, int32_t mode, float* out, void* ws,
+                          size_t ws_bytes, void* stream);
+
 /* ---- Pose video and track stitching ----
  * a2m_render_poses_u8 stands in for the drawing of generate_motion_video.py:66-164
  * (plot_head/body/hand_keypoints, draw_pose, draw_side_by_side_poses): every frame's P poses, each
