@@ -175,6 +175,8 @@ SIGNATURES = {
     'a2m_pck_f32': (ctypes.c_int, [P, P, I32, I32, F64, P, P]),
     'a2m_window_gather_f32': (ctypes.c_int, [P, I64, I32, P, I32, I32, I32, P, P, P, P]),
     'a2m_batch_gather_f32': (ctypes.c_int, [I32, P, P, P, P, P, P, P, P, P, P, I64, I32, P]),
+    'a2m_augment_params_f32': (ctypes.c_int, [P, I64, I32, P, U64, F32, F32, F32, F32, I32, I32, I32, I32, P, P]),
+    'a2m_batch_gather_aug_f32': (ctypes.c_int, [I32, P, P, P, P, P, P, P, P, P, P, P, P, I64, I32, P, P, F32, P]),
     'a2m_nn_search_ws_bytes': (SZ, [I32, I64]),
     'a2m_nn_search_f32': (ctypes.c_int, [P, P, I64, I64, I32, I32, I32, I32, P, P, P, I32, P, P, P, SZ, P]),
     'a2m_window_median_ws_bytes': (SZ, [I32]),

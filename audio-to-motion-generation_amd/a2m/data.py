@@ -11,6 +11,9 @@ Data_Loader for the pose and audio modalities, without pandas, h5py or a host co
               already normalised (audio, real_pose) that GANTrainer.fit and validate consume.
               A pass uploads one permutation; a batch is one launch of a2m_batch_gather_f32
               (csrc/data.hip), which reads the permutation on the device.
+  Augment     settings of the train-time augmentation that .pairs(..., augment=) applies inside
+              the gather (csrc/augment.hip): tempo, mirror, scale, gain, masks, drawn per clip on
+              the device from a counter-based generator; off by default
   dp_plan     which rows of which global batch a data-parallel rank takes
 
 Audio and pose of a clip come from the same sample of the same pass, and the poses are
@@ -36,6 +39,7 @@ COLUMNS = ('dataset', 'delta_time', 'end_time', 'interval_id', 'speaker', 'start
            'video_link')
 SPLITS = ('train', 'dev', 'test')
 MODE_RAW, MODE_STANDARDISE, MODE_NECKSUB = 0, 1, 2
+ROLE_NONE, ROLE_POSE, ROLE_AUDIO = 0, 1, 2      # what gather_augmented applies to a modality
 MAX_MOD = 4
 
 # Data_Loader arguments that select what is not built (text, samplers, sub-sampling), with the
@@ -218,6 +222,74 @@ def _i32s(vs):
     return (ctypes.c_int32 * len(vs))(*vs)
 
 
+class Augment:
+    """Settings of the train-time augmentation that PatsLoader.pairs(..., augment=) applies inside
+    its gather (csrc/augment.hip); every parameter is drawn per clip on the device, and everything
+    is off by default: Augment() is the identity.
+
+      seed        the Philox key; a clip's parameters depend on (seed, pass, start-table position) only
+      p_mirror    probability of a left-right mirrored pose (needs pose statistics), in [0, 1]
+      speed       tempo: both modalities are read at speed s, uniform in [1 - speed, 1 + speed]; in [0, 0.5]
+      scale       the neck-subtracted pose times g, uniform in [1 - scale, 1 + scale]; in [0, 1)
+      gain        added to the log-mel values, uniform in [-gain, gain]
+      freq_mask   one band of 0 .. freq_mask audio channels is written as mask_fill
+      time_mask   one run of 0 .. time_mask audio frames is written as mask_fill
+      first_pass  the pass number of the first iter() of a view; iter() k uses first_pass + k
+
+    The magnitudes are the caller's choice: which of these help on PATS has not been measured."""
+    NPARAM = 8      # mirror, s, g, gain, f0, fw, t0, tw
+
+    def __init__(self, seed=0, p_mirror=0., speed=0., scale=0., gain=0., freq_mask=0, time_mask=0,
+                 mask_fill=0., first_pass=0):
+        def real(name, v):
+            v = float(v)
+            if v != v or v in (float('inf'), float('-inf')):
+                raise ValueError(f'Augment: {name} must be finite, got {v}')
+            return v
+        self.seed, self.first_pass = int(seed), int(first_pass)
+        self.p_mirror, self.speed, self.scale = real('p_mirror', p_mirror), real('speed', speed), real('scale', scale)
+        self.gain, self.mask_fill = real('gain', gain), real('mask_fill', mask_fill)
+        self.freq_mask, self.time_mask = int(freq_mask), int(time_mask)
+        if not 0 <= self.seed < 2 ** 64:
+            raise ValueError(f'Augment: seed {seed} outside [0, 2^64)')
+        if not 0 <= self.first_pass < 2 ** 32:
+            raise ValueError(f'Augment: first_pass {first_pass} outside [0, 2^32)')
+        if not 0. <= self.p_mirror <= 1.:
+            raise ValueError(f'Augment: p_mirror {p_mirror} outside [0, 1]')
+        if not 0. <= self.speed <= 0.5:
+            raise ValueError(f'Augment: speed {speed} outside [0, 0.5]')
+        if not 0. <= self.scale < 1.:
+            raise ValueError(f'Augment: scale {scale} outside [0, 1)')
+        if self.gain < 0.:
+            raise ValueError(f'Augment: gain {gain} is negative')
+        if self.freq_mask != freq_mask or self.time_mask != time_mask or self.freq_mask < 0 or self.time_mask < 0:
+            raise ValueError(f'Augment: freq_mask {freq_mask} and time_mask {time_mask} must be integers >= 0')
+
+    def check_geometry(self, channels, frames):
+        if self.freq_mask > channels or self.time_mask > frames:
+            raise ValueError(f'Augment: freq_mask {self.freq_mask} / time_mask {self.time_mask} exceed the audio '
+                             f"window's {channels} channels / {frames} frames")
+
+    def draw(self, order_dev, b0, n, pass_dev, channels, frames, out=None):
+        """One launch: the float32 [n, 8] parameter table (columns mirror, s, g, gain, f0, fw, t0,
+        tw) of the clips order_dev[b0 : b0+n] for the pass number in pass_dev (device int64 [1]);
+        channels, frames: the audio window's C and T, which bound the masks."""
+        from . import functional as F
+        from ._native import check, lib
+        self.check_geometry(channels, frames)
+        if out is None:
+            out = torch.empty(n, self.NPARAM, device=order_dev.device)
+        F._check_dev(out)
+        if tuple(out.shape) != (n, self.NPARAM) or not out.is_contiguous():
+            raise ValueError(f'params must be a contiguous [{n}, {self.NPARAM}] tensor')
+        assert b0 >= 0 and order_dev.dtype == torch.int64 and order_dev.is_cuda and b0 + n <= order_dev.numel()
+        assert pass_dev.dtype == torch.int64 and pass_dev.is_cuda and pass_dev.numel() == 1
+        check(lib.a2m_augment_params_f32(F._p(order_dev), b0, n, F._p(pass_dev), self.seed, self.p_mirror,
+                                         self.speed, self.scale, self.gain, self.freq_mask, channels,
+                                         self.time_mask, frames, F._p(out), F._stream()))
+        return out
+
+
 class PatsLoader:
     """arrays: {interval_id: {modality: float32 [L, C] ndarray or tensor}} or the path of a
     save_arrays file.  The other arguments are Data_Loader's; rank / world shard every global
@@ -257,6 +329,7 @@ class PatsLoader:
             self.arena[mod] = torch.from_numpy(host).to(self.device)
             self.channels[mod] = C
         self._buffers, self._style_buffers = {}, {}
+        self._param_buffers, self._perm = {}, None
         self._upload_tables()
         for s in SPLITS:
             setattr(self, s, _DictView(self, s))
@@ -286,12 +359,17 @@ class PatsLoader:
         for s in SPLITS:
             self.base[s] = base
             base += ix.size(s)
-        self.start, style = {}, []
+        self.start, self.last, style = {}, {}, []
         for mod in self.modalities:
             rows = [self._row0[mod][iid] + w[mod][0][:n]
                     for s in SPLITS for iid, w, n in zip(ix.intervals[s], ix.windows[s], ix.sizes[s])]
             host = np.concatenate(rows).astype(np.int64) if rows else np.zeros(0, np.int64)
             self.start[mod] = torch.from_numpy(host).to(self.device)
+            # beside start: the arena row of the last row of each sample's interval, where the
+            # augmenting gather clamps a stretched read
+            ends = [np.full(n, self._row0[mod][iid] + int(ix.lengths[iid][mod]) - 1, np.int64)
+                    for s in SPLITS for iid, n in zip(ix.intervals[s], ix.sizes[s])]
+            self.last[mod] = torch.from_numpy(np.concatenate(ends) if ends else np.zeros(0, np.int64)).to(self.device)
         for s in SPLITS:
             style += [np.full(n, ix.style[iid], np.float32) for iid, n in zip(ix.intervals[s], ix.sizes[s])]
         self._style = torch.from_numpy(np.concatenate(style) if style else np.zeros(0, np.float32)).to(self.device)
@@ -363,11 +441,45 @@ class PatsLoader:
             F._stream()))
         return outs
 
+    def gather_augmented(self, order_dev, b0, n, specs, params, outs=None, mask_fill=0.):
+        """gather() with row b of params (float32 [n, 8], Augment.draw's or the caller's: mirror, s,
+        g, gain, f0, fw, t0, tw) applied to clip b, one launch.  A pose modality in the neck-sub
+        mode is mirrored and scaled, an audio modality takes the gain and the masks, every
+        modality the tempo.  A caller's table keeps s >= 0 and the masks inside the window."""
+        from . import functional as F
+        from ._native import check, lib
+        from .skeleton import mirror_permutation
+        mods = [s[0] for s in specs]
+        geo = [self.index.geometry(m) for m in mods]
+        if outs is None:
+            outs = [torch.empty(n, g[2], self.channels[m], device=self.device) for m, g in zip(mods, geo)]
+        means, stds = [s[2] for s in specs], [s[3] for s in specs]
+        F._check_dev(*outs, *means, *stds, params)
+        for m, g, out, mean, std in zip(mods, geo, outs, means, stds):
+            if tuple(out.shape) != (n, g[2], self.channels[m]) or not out.is_contiguous():
+                raise ValueError(f'{m}: out must be a contiguous [{n}, {g[2]}, {self.channels[m]}] tensor')
+            if any(t is not None and (t.numel() != self.channels[m] or not t.is_contiguous()) for t in (mean, std)):
+                raise ValueError(f'{m}: mean and std must be contiguous [{self.channels[m]}] tensors')
+        if tuple(params.shape) != (n, Augment.NPARAM) or not params.is_contiguous():
+            raise ValueError(f'params must be a contiguous [{n}, {Augment.NPARAM}] tensor')
+        assert b0 >= 0 and order_dev.dtype == torch.int64 and order_dev.is_cuda and b0 + n <= order_dev.numel()
+        roles = [ROLE_POSE if m.startswith('pose') and s[1] == MODE_NECKSUB else
+                 ROLE_AUDIO if m.startswith('audio') else ROLE_NONE for m, s in zip(mods, specs)]
+        if self._perm is None:
+            self._perm = torch.tensor(mirror_permutation(), dtype=torch.int32).to(self.device)
+        check(lib.a2m_batch_gather_aug_f32(
+            len(specs), _ptrs([self.arena[m] for m in mods]), _ptrs([self.start[m] for m in mods]),
+            _ptrs([self.last[m] for m in mods]), _i32s([self.channels[m] for m in mods]),
+            _i32s([g[0] for g in geo]), _i32s([g[1] for g in geo]), _i32s([s[1] for s in specs]), _i32s(roles),
+            _ptrs(means), _ptrs(stds), _ptrs(outs), F._p(order_dev), b0, n, F._p(params), F._p(self._perm),
+            float(mask_fill), F._stream()))
+        return outs
+
     def _stat(self, t):
         return None if t is None else torch.as_tensor(t).to(self.device, torch.float32).contiguous()
 
     def pairs(self, split, pose_mean=None, pose_std=None, audio_mean=None, audio_std=None, copy=False,
-              order=None, with_style=False):
+              order=None, with_style=False, augment=None):
         """A re-iterable of (audio [n, T, 128], real_pose [n, T, 104]) for GANTrainer.fit /
         validate, one launch a batch.  With pose statistics the poses are neck-subtracted and
         normalised as necksub_normalize, with audio statistics the audio is standardised as
@@ -376,9 +488,20 @@ class PatsLoader:
         next is formed, on one stream); copy=True yields fresh tensors for callers that keep
         batches.  order: the caller's order of the split's global indices instead of a drawn one.
         with_style=True yields (audio, real_pose, style), style the int32 [n] speaker ids of the
-        batch's clips, looked up on the device (one more launch a batch, no synchronisation)."""
+        batch's clips, looked up on the device (one more launch a batch, no synchronisation).
+        augment: an Augment; each batch is then the parameter draw plus the augmenting gather (two
+        launches, no synchronisation), iter() number k of the view draws for pass
+        augment.first_pass + k, and the view's last_params is the device table of the batch just
+        yielded.  Mirroring and scaling act on the neck-subtracted pose and need pose statistics
+        (left-right symmetric ones, for a mirrored pose to be normalised like its original)."""
         if (pose_mean is None) != (pose_std is None) or (audio_mean is None) != (audio_std is None):
             raise ValueError('mean and std come together')
+        if augment is not None:
+            if not isinstance(augment, Augment):
+                raise TypeError('augment must be an a2m.data.Augment')
+            if pose_mean is None and (augment.p_mirror > 0 or augment.scale > 0):
+                raise ValueError('augment: p_mirror and scale act on the neck-subtracted pose and need '
+                                 'pose_mean / pose_std')
         if order is not None:
             order = self.draw(split, order)     # refused here, on the host, before any launch
         pose =next(m for m in self.modalities if m.startswith('pose'))
@@ -387,7 +510,9 @@ class PatsLoader:
                   self._stat(audio_std)),
                  (pose, MODE_RAW if pose_mean is None else MODE_NECKSUB, self._stat(pose_mean),
                   self._stat(pose_std))]
-        return _Pairs(self, split, specs, copy, order, with_style)
+        if augment is not None:
+            augment.check_geometry(self.channels[audio], self.index.geometry(audio)[2])
+        return _Pairs(self, split, specs, copy, order, with_style, augment)
 
 
 class _View:
@@ -409,15 +534,41 @@ class _View:
 
 
 class _Pairs(_View):
-    def __init__(self, loader, split, specs, copy, order, with_style=False):
+    def __init__(self, loader, split, specs, copy, order, with_style=False, augment=None):
         super().__init__(loader, split, order)
         self.specs, self.copy, self.with_style = specs, copy, with_style
+        self.augment, self.passes, self.pass_dev, self.last_params = augment, 0, None, None
 
-    def _run(self, host, order_dev, plan):
+    def __iter__(self):
+        if self.augment is None:
+            return super().__iter__()
+        # the pass number goes up next to the order, in a scalar of this pass's own: an iterator
+        # of an earlier pass that is still being consumed keeps its number
+        ld = self.loader
+        host = ld.draw(self.split, self.order)
+        plan = dp_plan(len(host), ld.batch_size, ld.rank, ld.world)[0]
+        self.pass_dev = torch.tensor([self.augment.first_pass + self.passes], dtype=torch.int64).to(ld.device)
+        self.passes += 1
+        return self._run(host, ld.upload(self.split, host) if len(host) else None, plan, self.pass_dev)
+
+    def _gather_augmented(self, order_dev, b0, n, outs, pass_dev):
+        ld, aug = self.loader, self.augment
+        audio = self.specs[0][0]
+        params = None if self.copy else ld._param_buffers.get(n)
+        params = aug.draw(order_dev, b0, n, pass_dev, ld.channels[audio], ld.index.geometry(audio)[2], params)
+        if not self.copy:
+            ld._param_buffers[n] = params
+        self.last_params = params
+        return ld.gather_augmented(order_dev, b0, n, self.specs, params, outs, aug.mask_fill)
+
+    def _run(self, host, order_dev, plan, pass_dev=None):
         ld = self.loader
         for b0, n in plan:
             outs = None if self.copy else ld._buffers.get(n)
-            outs = ld.gather(order_dev, b0, n, self.specs, outs)
+            if pass_dev is None:
+                outs = ld.gather(order_dev, b0, n, self.specs, outs)
+            else:
+                outs = self._gather_augmented(order_dev, b0, n, outs, pass_dev)
             if not self.copy:
                 ld._buffers[n] = outs
             if not self.with_style:

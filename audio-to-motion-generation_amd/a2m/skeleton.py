@@ -25,6 +25,15 @@ FPS = 15
 NUM_BODY, NUM_HAND, FEAT = 10, 42, 64
 
 
+def mirror_permutation():
+    """perm[k]: the joint that joint k of a left-right mirrored pose is read from, from JOINT_NAMES
+    by swapping a leading 'R' / 'L' (Neck and Nose have no counterpart and stay): 1<->4, 2<->5,
+    3<->6, 8<->9, 10+k<->31+k for k in 0..20.  An involution."""
+    swap = {'R': 'L', 'L': 'R'}
+    index = {name: k for k, name in enumerate(JOINT_NAMES)}
+    return [index.get(swap.get(name[0], '') + name[1:], k) for k, name in enumerate(JOINT_NAMES)]
+
+
 class Skeleton2D:
     """Constant-only stand-in for pats.data_loading.Skeleton2D (no dataset access)."""
     parents = PARENTS

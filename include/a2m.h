@@ -894,6 +894,58 @@ int a2m_batch_gather_f32(int32_t n_mod, const float* const* arena, const int64_t
                          const int32_t* mode, const float* const* mean, const float* const* std_,
                          float* const* out, const int64_t* order, int64_t b0, int32_t n, void* stream);
 
+/* ---- Train-time augmentation inside the loader's gather (a2m.data.Augment; csrc/augment.hip) ----
+ * a2m_augment_params_f32 fills params[b][8] (device float32) for the clips pos = order[b0 + b],
+ * b < n, one launch, no host synchronisation.  Columns: mirror (0 / 1), s, g, gain, f0, fw, t0, tw.
+ * The generator is Philox4x32-10 with key (seed & 0xffffffff, seed >> 32) and counter
+ * (pos & 0xffffffff, pos >> 32, (uint32) pass[0], call); pass is a device int64[1] read by the kernel,
+ * so a captured launch follows an overwritten pass number.  u = float(x >> 8) * 2^-24 of an output
+ * word x.  Call 0, words 0..3: mirror = u0 < p_mirror; s = 1 + r_speed (2 u1 - 1);
+ * g = 1 + r_scale (2 u2 - 1); gain = r_gain (2 u3 - 1).  Call 1: fw = floor(u0 (max_fw + 1));
+ * f0 = floor(u1 (C - fw + 1)); tw = floor(u2 (max_tw + 1)); t0 = floor(u3 (T - tw + 1)).  Every
+ * float step is rounded once to fp32 (2u and 2u - 1 are exact).  A clip's row depends on (seed,
+ * pass[0], pos) only: not on n, b0 or b.
+ * A2M_EINVAL ("augment_params: ...") before any launch: n < 0 or b0 < 0; p_mirror outside [0, 1];
+ * r_speed outside [0, 0.5]; r_scale outside [0, 1); r_gain negative or not finite; C or T outside
+ * 1 .. 2^24 - 1; max_fw outside [0, C]; max_tw outside [0, T]; with n > 0 a NULL order, pass or
+ * params.  n = 0 returns A2M_OK without a launch.
+ *
+ * a2m_batch_gather_aug_f32 is a2m_batch_gather_f32 with the row b of params applied to clip b.
+ * last[m]: int64 device table beside start[m], the arena row of the last row of each sample's
+ * interval.  role[m]: A2M_AUGMENT_NONE, A2M_AUGMENT_POSE (mode A2M_BATCH_NECKSUB only) or
+ * A2M_AUGMENT_AUDIO (modes RAW and STANDARDISE).  perm: int32[52] device table, the source joint of
+ * each output joint of a mirrored clip (entries outside [0, 52) read the joint itself).
+ *   tempo, every role: output frame j reads row position p = fl(float(j * interval[m]) * s) from the
+ *     sample's start (clamped to [0, 2^24]); i = floor(p), f = p - i; a = row min(start + i, last),
+ *     b = row min(start + i + 1, last); the value is a where f == 0 (row b is then not read, so
+ *     s == 1 is a2m_batch_gather_f32 bit for bit) and a + f (b - a) otherwise, three roundings.
+ *   A2M_BATCH_NECKSUB: d = v[src] - v[neck] over the interpolated channels of the same plane, src =
+ *     perm[k] for a mirrored clip of the pose role, else k; pose role: d = -d in the x plane when
+ *     mirrored, then d = d * g; out = (d - mean[c]) / std[c] with the output channel's statistics.
+ *   audio role: gain, where non-zero, is added to the interpolated value before the mode's
+ *     arithmetic; afterwards channels [f0, f0 + fw) of every frame and frames [t0, t0 + tw) of every
+ *     channel are written as mask_fill.  A width of 0 masks nothing.
+ * The kernel checks no bounds beyond the clamp at last: the caller guarantees order, start and last
+ * as for a2m_batch_gather_f32, last >= start, and params [n][8].  No host synchronisation; captures
+ * into a HIP graph.  A2M_EINVAL ("batch_gather_aug: ...") before any launch for everything
+ * a2m_batch_gather_f32 refuses, a NULL last, role, params or perm, an unknown role, the pose role
+ * on a mode other than NECKSUB, the audio role on NECKSUB, window >= 2^24.  n = 0 returns A2M_OK
+ * without a launch and accepts NULL pointers. */
+#define A2M_AUGMENT_NPARAM 8
+#define A2M_AUGMENT_NONE 0
+#define A2M_AUGMENT_POSE 1
+#define A2M_AUGMENT_AUDIO 2
+int a2m_augment_params_f32(const int64_t* order, int64_t b0, int32_t n, const int64_t* pass,
+                           uint64_t seed, float p_mirror, float r_speed, float r_scale, float r_gain,
+                           int32_t max_fw, int32_t C, int32_t max_tw, int32_t T, float* params,
+                           void* stream);
+int a2m_batch_gather_aug_f32(int32_t n_mod, const float* const* arena, const int64_t* const* start,
+                             const int64_t* const* last, const int32_t* C, const int32_t* window,
+                             const int32_t* interval, const int32_t* mode, const int32_t* role,
+                             const float* const* mean, const float* const* std_, float* const* out,
+                             const int64_t* order, int64_t b0, int32_t n, const float* params,
+                             const int32_t* perm, float mask_fill, void* stream);
+
 /* ---- Evaluation baselines over the loader's arena (a2m/baselines.py; csrc/baselines.hip) ----
  * Both entries address windows exactly as a2m_batch_gather_f32 does: the window at table position p
  * is the rows arena[start[p] + j*interval], j < T = ceil(window / interval), of an arena
