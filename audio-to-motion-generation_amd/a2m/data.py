@@ -16,6 +16,10 @@ Data_Loader for the pose and audio modalities, without pandas, h5py or a host co
               the device from a counter-based generator; off by default
   dp_plan     which rows of which global batch a data-parallel rank takes
 
+PatsLoader.train_sampler gives the reference's train samplers (a2m/sampling.py: alternating
+speakers, few-shot, the velocity quantiles and bins, weighted, fixed iterations);
+.pairs(..., sampler=) and .sampled(split, sampler) draw each pass's order from one.
+
 Audio and pose of a clip come from the same sample of the same pass, and the poses are
 normalised in the gather: the reference's two separately shuffled passes
 (version5_model_train.py:296-319) have no counterpart here.
@@ -42,8 +46,9 @@ MODE_RAW, MODE_STANDARDISE, MODE_NECKSUB = 0, 1, 2
 ROLE_NONE, ROLE_POSE, ROLE_AUDIO = 0, 1, 2      # what gather_augmented applies to a modality
 MAX_MOD = 4
 
-# Data_Loader arguments that select what is not built (text, samplers, sub-sampling), with the
-# only value accepted for each: the reference's default
+# Data_Loader arguments the constructor refuses, with the only value accepted for each, the
+# reference's default: the text options are not built, and the train samplers are asked for
+# through PatsLoader.train_sampler (a2m/sampling.py), not here
 UNSUPPORTED = {'style_iters': 0, 'num_training_sample': None, 'sample_all_styles': 0, 'repeat_text': 1,
                'quantile_sample': None, 'quantile_num_training_sample': None, 'weighted': 0,
                'filler': False, 'num_training_iters': None}
@@ -330,6 +335,7 @@ class PatsLoader:
             self.channels[mod] = C
         self._buffers, self._style_buffers = {}, {}
         self._param_buffers, self._perm = {}, None
+        self._velocity, self._velocity_bad = {}, {}
         self._upload_tables()
         for s in SPLITS:
             setattr(self, s, _DictView(self, s))
@@ -377,6 +383,8 @@ class PatsLoader:
         self._style_i32 = torch.from_numpy(np.concatenate(style).astype(np.int32) if style
                                            else np.zeros(0, np.int32)).to(self.device)
         self._meta = {}
+        self._velocity.clear()
+        self._velocity_bad.clear()
         self.dropped = {s: dp_plan(ix.size(s), self.batch_size, self.rank, self.world)[1] for s in SPLITS}
         self._buffers.clear()
 
@@ -398,6 +406,47 @@ class PatsLoader:
         ids, times, local = self._meta[split]
         return {'interval_id': [ids[i] for i in idx], 'start': torch.from_numpy(times[idx, 0]),
                 'end': torch.from_numpy(times[idx, 1]), 'idx': torch.from_numpy(local[idx])}
+
+    # ------------------------------------------------------------------ train samplers
+    def clip_velocity(self, split):
+        """The mean joint speed (pixels per frame, a2m.functional.clip_velocity) of every clip of
+        the split in global-index order: float32 [N] on the device, read from the pose arena in
+        place at the loader's geometry, computed once per split and kept until update_dataloaders."""
+        if split not in self._velocity:
+            from . import functional as F
+            pose = next(m for m in self.modalities if m.startswith('pose'))
+            window, interval, _ = self.index.geometry(pose)
+            self._velocity[split], self._velocity_bad[split] = F.clip_velocity(
+                self.arena[pose], self.start[pose], self.base[split], self.index.size(split), window, interval)
+        return self._velocity[split]
+
+    def train_sampler(self, split='train', *, style_iters=0, num_training_sample=None, quantile_sample=None,
+                      quantile_num_training_sample=None, weighted=0, num_training_iters=None,
+                      sample_all_styles=0, velocity=None, generator=None):
+        """The reference's train sampler for its arguments style_iters, num_training_sample,
+        quantile_sample, quantile_num_training_sample, weighted and num_training_iters, in its
+        precedence (a2m.sampling.make_sampler, which documents each): a TrainSampler for
+        pairs(..., sampler=) and sampled(), or None where nothing is set.  velocity=: a host array
+        [N] to bin by instead of clip_velocity(split); generator=: feeds every draw (default: the
+        loader's, else torch's global one).  Construction may synchronise; a pass does not."""
+        from .sampling import make_sampler
+        return make_sampler(self, split, style_iters=style_iters, num_training_sample=num_training_sample,
+                            quantile_sample=quantile_sample,
+                            quantile_num_training_sample=quantile_num_training_sample, weighted=weighted,
+                            num_training_iters=num_training_iters, sample_all_styles=sample_all_styles,
+                            velocity=velocity, generator=generator)
+
+    def sampled(self, split, sampler):
+        """The batch-dict view of .train / .dev / .test over the sampler's order: every iter() is a
+        new draw."""
+        self._check_sampler(split, sampler)
+        return _DictView(self, split, sampler=sampler)
+
+    def _check_sampler(self, split, sampler):
+        # the gather checks no index: a sampler built for another split or other windows is refused here
+        if sampler.split != split or sampler.n != self.index.size(split):
+            raise ValueError(f'sampler: built for the {sampler.n} clips of {sampler.split}, not the '
+                             f'{self.index.size(split)} of {split}')
 
     # ------------------------------------------------------------------ one pass
     def draw(self, split, order=None):
@@ -479,7 +528,7 @@ class PatsLoader:
         return None if t is None else torch.as_tensor(t).to(self.device, torch.float32).contiguous()
 
     def pairs(self, split, pose_mean=None, pose_std=None, audio_mean=None, audio_std=None, copy=False,
-              order=None, with_style=False, augment=None):
+              order=None, with_style=False, augment=None, sampler=None):
         """A re-iterable of (audio [n, T, 128], real_pose [n, T, 104]) for GANTrainer.fit /
         validate, one launch a batch.  With pose statistics the poses are neck-subtracted and
         normalised as necksub_normalize, with audio statistics the audio is standardised as
@@ -493,7 +542,13 @@ class PatsLoader:
         launches, no synchronisation), iter() number k of the view draws for pass
         augment.first_pass + k, and the view's last_params is the device table of the batch just
         yielded.  Mirroring and scaling act on the neck-subtracted pose and need pose statistics
-        (left-right symmetric ones, for a mirrored pose to be normalised like its original)."""
+        (left-right symmetric ones, for a mirrored pose to be normalised like its original).
+        sampler: a train_sampler(); every iter() then takes a new draw of it as the pass's order
+        (not together with order=), and len() follows its length."""
+        if sampler is not None:
+            if order is not None:
+                raise ValueError('sampler and order both name the pass\'s order: give one')
+            self._check_sampler(split, sampler)
         if (pose_mean is None) != (pose_std is None) or (audio_mean is None) != (audio_std is None):
             raise ValueError('mean and std come together')
         if augment is not None:
@@ -512,30 +567,37 @@ class PatsLoader:
                   self._stat(pose_std))]
         if augment is not None:
             augment.check_geometry(self.channels[audio], self.index.geometry(audio)[2])
-        return _Pairs(self, split, specs, copy, order, with_style, augment)
+        return _Pairs(self, split, specs, copy, order, with_style, augment, sampler)
 
 
 class _View:
-    def __init__(self, loader, split, order=None):
-        self.loader, self.split, self.order = loader, split, order
+    def __init__(self, loader, split, order=None, sampler=None):
+        self.loader, self.split, self.order, self.sampler = loader, split, order, sampler
 
     def __len__(self):
-        if self.order is not None:
-            return len(dp_plan(len(self.order), self.loader.batch_size, self.loader.rank, self.loader.world)[0])
+        fixed = self.sampler if self.sampler is not None else self.order
+        if fixed is not None:
+            return len(dp_plan(len(fixed), self.loader.batch_size, self.loader.rank, self.loader.world)[0])
         return len(self.loader.plan(self.split))
+
+    def _draw(self):
+        if self.sampler is None:
+            return self.loader.draw(self.split, self.order)
+        self.loader._check_sampler(self.split, self.sampler)
+        return self.sampler.draw()
 
     def __iter__(self):
         # the draw and the upload happen here, not at the first next(): the loop that follows
         # crosses the bus no more
         ld = self.loader
-        host = ld.draw(self.split, self.order)
+        host = self._draw()
         plan = dp_plan(len(host), ld.batch_size, ld.rank, ld.world)[0]
         return self._run(host, ld.upload(self.split, host) if len(host) else None, plan)
 
 
 class _Pairs(_View):
-    def __init__(self, loader, split, specs, copy, order, with_style=False, augment=None):
-        super().__init__(loader, split, order)
+    def __init__(self, loader, split, specs, copy, order, with_style=False, augment=None, sampler=None):
+        super().__init__(loader, split, order, sampler)
         self.specs, self.copy, self.with_style = specs, copy, with_style
         self.augment, self.passes, self.pass_dev, self.last_params = augment, 0, None, None
 
@@ -545,7 +607,7 @@ class _Pairs(_View):
         # the pass number goes up next to the order, in a scalar of this pass's own: an iterator
         # of an earlier pass that is still being consumed keeps its number
         ld = self.loader
-        host = ld.draw(self.split, self.order)
+        host = self._draw()
         plan = dp_plan(len(host), ld.batch_size, ld.rank, ld.world)[0]
         self.pass_dev = torch.tensor([self.augment.first_pass + self.passes], dtype=torch.int64).to(ld.device)
         self.passes += 1

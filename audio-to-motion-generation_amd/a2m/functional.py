@@ -1374,6 +1374,64 @@ def window_median(arena, start, lo, n, window, interval, necksub=False):
     return out
 
 
+def clip_velocity(arena, start, lo, n, window, interval):
+    """Mean 2-D speed of the non-neck joints, pixels per frame, of the clips at table positions
+    [lo, lo + n) of start (a2m_clip_velocity_f32): arena [rows, C] in the loader's planar pose
+    layout (x in channels 0 .. C/2 - 1, y behind them, joint 0 the neck), read in place.  Returns
+    (velocity float32 [n], n_nonfinite int32 [1]: the number of clips whose velocity is not
+    finite), both on the device.  No host synchronisation."""
+    if int(n) == 0:
+        _check_dev(arena)
+        return torch.empty(0, device=arena.device), torch.zeros(1, dtype=torch.int32, device=arena.device)
+    lo, n = _check_table(arena, start, lo, n, 'clip_velocity')
+    out = torch.empty(n, device=arena.device)
+    bad = torch.empty(1, dtype=torch.int32, device=arena.device)
+    N.check(N.lib.a2m_clip_velocity_f32(_p(arena), _p(start), lo, n, arena.shape[1], int(window), int(interval),
+                                        _p(out), _p(bad), _stream()), value_error=True)
+    return out, bad
+
+
+def select(x, ranks):
+    """Exact order statistics of x (float32 [n] on the device, every value non-negative and finite):
+    the elements at `ranks` (1 .. 8 host integers in [0, n), repeats allowed) of the ascending order
+    (a2m_select_f32, a radix select: no sort).  Returns (values float32 [k], minmax float32 [2]: the
+    smallest and the largest value), both on the device.  No host synchronisation."""
+    _check_dev(x)
+    if x.dim() != 1 or not x.is_contiguous() or x.numel() == 0:
+        raise ValueError('select: x must be a contiguous, non-empty [n] tensor')
+    ranks = [int(r) for r in ranks]
+    k, n = len(ranks), x.numel()
+    out = torch.empty(k, device=x.device)
+    minmax = torch.empty(2, device=x.device)
+    ws = torch.empty(max(N.lib.a2m_select_f32_ws_bytes(n), 4), dtype=torch.uint8, device=x.device)
+    N.check(N.lib.a2m_select_f32(_p(x), n, (ctypes.c_int64 * k)(*ranks), k, _p(out), _p(minmax), _p(ws),
+                                 ws.numel(), _stream()), value_error=True)
+    return out, minmax
+
+
+CLASSIFY_KINDS = {'above': 0, 'tail': 1, 'bins': 2}
+
+
+def classify(x, kind, thr):
+    """The class of every x[i] (float32 [n] on the device) against the host thresholds thr, compared
+    in float64 (a2m_classify_f32).  kind 'above' (one threshold): 0 if x > thr[0]; 'tail' (two): 0
+    if x > thr[1] or x < thr[0]; 'bins' (q + 1 ascending edges): the first j with thr[j] <= x <=
+    thr[j+1], a value on an inner edge in the lower bin; -1 otherwise.  Returns (cls int32 [n],
+    counts int64 [n_cls]) on the device, n_cls = 1, 1, q.  No host synchronisation."""
+    _check_dev(x)
+    if x.dim() != 1 or not x.is_contiguous():
+        raise ValueError('classify: x must be a contiguous [n] tensor')
+    if kind not in CLASSIFY_KINDS:
+        raise ValueError(f'classify: unknown kind {kind!r}')
+    thr = [float(t) for t in thr]
+    n_cls = max(len(thr) - 1, 1) if kind == 'bins' else 1
+    cls = torch.empty(x.numel(), dtype=torch.int32, device=x.device)
+    counts = torch.zeros(n_cls, dtype=torch.int64, device=x.device)
+    N.check(N.lib.a2m_classify_f32(_p(x), x.numel(), CLASSIFY_KINDS[kind], (ctypes.c_double * len(thr))(*thr),
+                                   len(thr), _p(cls), _p(counts), _stream()), value_error=True)
+    return cls, counts
+
+
 def gather_segments_(dst, segments):
     """dst[off:off + t.numel()] = t.reshape(-1) for every (off, t) in segments (contiguous fp32
     device tensors), 48 segments per launch (a2m_gather_segments_f32)."""

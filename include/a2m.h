@@ -995,6 +995,66 @@ int a2m_window_median_f32(const float* arena, const int64_t* start, int64_t lo, 
                           int32_t window, int32_t interval, int32_t mode, float* out, void* ws,
                           size_t ws_bytes, void* stream);
 
+/* ---- Train samplers over the loader's arena (a2m/sampling.py; csrc/sampling.hip) ----
+ * The device half of PatsLoader.train_sampler: the mean joint speed of every clip of a split, exact
+ * order statistics of those speeds, and the binning of the clips.  All three take a stream, issue no
+ * host synchronisation, capture into a HIP graph (one memset node ahead of the velocity and the
+ * classify kernel, one ahead of the select passes), use no floating-point atomics, and give
+ * byte-identical results from run to run.
+ *
+ * a2m_clip_velocity_f32: clip i in [lo, lo + n) of a start table is the rows r_t = start[i] +
+ * t*interval, t < T = ceil(window / interval), of arena [rows][C] float32 in the loader's planar
+ * pose layout: K = C/2 joints, x of joint j in channel j, y in channel K + j, joint 0 the neck.
+ *   out[i - lo] = mean over t = 1 .. T-1 and j = 1 .. K-1 of
+ *                 sqrt((x[r_t][j] - x[r_t-1][j])^2 + (x[r_t][K+j] - x[r_t-1][K+j])^2)
+ * the mean 2-D speed of the non-neck joints in pixels per frame.  Every term is computed in fp32
+ * (two differences, the sum of squares, a correctly rounded root); one wave owns a clip, every lane
+ * adds its terms in double in a fixed order, the lanes are combined by a fixed tree, and the mean
+ * is rounded once to float: the value is a function of the clip's rows alone.  n_nonfinite (device
+ * int32, zeroed here) receives the number of clips whose result is not finite (an integer atomic).
+ * The kernel checks no bounds: the caller guarantees start[lo .. lo+n) and start + window within
+ * the arena.
+ * A2M_EINVAL ("clip_velocity: ...") before any launch: n < 0 or lo < 0; with n > 0 a NULL arena,
+ * start, out or n_nonfinite; C odd or C < 4 (fewer than two joints); window <= 0 or interval <= 0;
+ * T < 2; (T-1)*(K-1) or n >= 2^31.  n == 0 is A2M_OK without a launch, whatever the other arguments.
+ *
+ * a2m_select_f32: out[w] = the element at rank ranks[w] (host int64[k], 1 <= k <=
+ * A2M_SELECT_MAX_RANKS, 0 <= rank < n, repeats allowed) of the ascending order of the n values x
+ * (device float32, every one non-negative and finite: such floats order as their bit patterns, which
+ * is what is compared, so +0 and subnormals keep their place); minmax[0], minmax[1] the smallest and
+ * the largest.  A radix select, 8 bits a pass from the top, four passes, every rank carried at once:
+ * a histogram kernel (LDS and global integer atomics) and a one-wave kernel that walks the 256
+ * counts to each rank's bucket; the bucket is chosen on the device.  Exact.  ws:
+ * a2m_select_f32_ws_bytes(n) bytes, 4-byte aligned.
+ * A2M_EINVAL ("select: ...") before any launch: n < 0 or n >= 2^32; with n > 0 a NULL x, ranks, out,
+ * minmax or ws; k outside 1..A2M_SELECT_MAX_RANKS; a rank outside [0, n); ws misaligned or ws_bytes
+ * too small.  n == 0 is A2M_OK without a launch.
+ *
+ * a2m_classify_f32: cls[i] (device int32) is the class of x[i] (device float32) against thr (host
+ * double[n_thr]; the comparison is done in double, to which the float converts exactly), counts[c]
+ * (device int64[n_cls], zeroed here) the number of elements of class c, n_cls = 1 for ABOVE and
+ * TAIL and n_thr - 1 for BINS; integer adds only.
+ *   A2M_CLASSIFY_ABOVE (n_thr 1)  0 if x > thr[0], else -1
+ *   A2M_CLASSIFY_TAIL  (n_thr 2)  0 if x > thr[1] or x < thr[0], else -1
+ *   A2M_CLASSIFY_BINS  (n_thr q+1 ascending edges)  the first j with thr[j] <= x <= thr[j+1]: both
+ *                      ends closed, a value on an inner edge in the lower bin; -1 if none (NaN too)
+ * A2M_EINVAL ("classify: ...") before any launch: n < 0; an unknown kind; with n > 0 a NULL x, thr,
+ * cls or counts; n_thr not as the kind requires (BINS: 2 .. A2M_CLASSIFY_MAX_THR); a NaN threshold;
+ * BINS edges that descend.  n == 0 is A2M_OK without a launch. */
+#define A2M_SELECT_MAX_RANKS 8
+#define A2M_CLASSIFY_ABOVE 0
+#define A2M_CLASSIFY_TAIL 1
+#define A2M_CLASSIFY_BINS 2
+#define A2M_CLASSIFY_MAX_THR 257
+int a2m_clip_velocity_f32(const float* arena, const int64_t* start, int64_t lo, int64_t n, int32_t C,
+                          int32_t window, int32_t interval, float* out, int32_t* n_nonfinite,
+                          void* stream);
+size_t a2m_select_f32_ws_bytes(int64_t n);
+int a2m_select_f32(const float* x, int64_t n, const int64_t* ranks, int32_t k, float* out,
+                   float* minmax, void* ws, size_t ws_bytes, void* stream);
+int a2m_classify_f32(const float* x, int64_t n, int32_t kind, const double* thr, int32_t n_thr,
+                     int32_t* cls, int64_t* counts, void* stream);
+
 /* ---- Pose video and track stitching ----
  * a2m_render_poses_u8 stands in for the drawing of generate_motion_video.py:66-164
  * (plot_head/body/hand_keypoints, draw_pose, draw_side_by_side_poses): every frame's P poses, each
