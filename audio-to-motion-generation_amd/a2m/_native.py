@@ -181,6 +181,11 @@ SIGNATURES = {
     'a2m_nn_search_f32': (ctypes.c_int, [P, P, I64, I64, I32, I32, I32, I32, P, P, P, I32, P, P, P, SZ, P]),
     'a2m_window_median_ws_bytes': (SZ, [I32]),
     'a2m_window_median_f32': (ctypes.c_int, [P, P, I64, I64, I32, I32, I32, I32, P, P, SZ, P]),
+    'a2m_coverage_store_f32': (ctypes.c_int, [P, P, P, P, P, I32, I32, I32, I32, I64, I64, P, P, P, P]),
+    'a2m_pair_dist2_ws_bytes': (SZ, [I64, I64]),
+    'a2m_pair_dist2_f32': (ctypes.c_int, [P, I64, P, I64, P, I64, P, I64, I64, I32, I64, P, SZ, P]),
+    'a2m_row_kth_f32': (ctypes.c_int, [P, I64, I64, I32, I32, P, P, P]),
+    'a2m_row_cover_f32': (ctypes.c_int, [P, I64, I64, P, P, P, P]),
     'a2m_clip_velocity_f32': (ctypes.c_int, [P, P, I64, I64, I32, I32, I32, P, P, P]),
     'a2m_select_f32_ws_bytes': (SZ, [I64]),
     'a2m_select_f32': (ctypes.c_int, [P, I64, P, I32, P, P, P, SZ, P]),

@@ -51,6 +51,12 @@ each for the real pose (the ceiling a generator can be held to) and the generate
 onset_delta = 1.0 and beat_sigma = 1.0 frame (67 ms at 15 fps; AIST++ uses 50 ms) are guesses like
 the histogram range: nobody has looked at PATS onsets at 15 fps.  beat_far_share is the share of
 the motion beats in the last distance bin.
+
+CoverageEvaluator / evaluate(..., coverage=True): all of the above pool frames, so a generator that
+emits one plausible clip for every audio window scores well.  The opt-in set metrics over whole clips
+(COVERAGE_METRICS) single it out: improved precision and recall, density and coverage,
+and the mean pairwise distance among the generated and among the real clips; the class docstring has
+the definitions.
 """
 import numpy as np
 import torch
@@ -63,6 +69,7 @@ METRICS = ('pck', 'l1', 'fd', 'w1_speed', 'w1_accel', 'mean_speed_real', 'mean_s
 SYNC_METRICS = ('beat_align_real', 'beat_align_fake', 'beat_recall_real', 'beat_recall_fake', 'sync_corr_real',
                 'sync_corr_fake', 'sync_lag_real', 'sync_lag_fake', 'n_audio_beats', 'n_motion_beats_real',
                 'n_motion_beats_fake', 'beat_far_share')
+COVERAGE_METRICS = ('precision', 'recall', 'density', 'coverage', 'diversity_fake', 'diversity_real', 'n_coverage')
 
 
 def compute_pck(pred, gt, alpha=0.2):
@@ -328,8 +335,182 @@ class AudioSyncEvaluator:
         return out
 
 
+def _coverage_metrics(k, kth_real, cnt_prec, cnt_rec, min_rg, sum_real, sum_fake):
+    """One entry of CoverageEvaluator.result() from one set's per-row vectors on the host."""
+    m = len(kth_real)
+    if m <= k:
+        out = dict.fromkeys(COVERAGE_METRICS, float('nan'))
+    else:
+        pairs = float(m) * (m - 1)
+        out = {'precision': float(np.count_nonzero(cnt_prec > 0)) / m,
+               'recall': float(np.count_nonzero(cnt_rec > 0)) / m,
+               'density': float(cnt_prec.astype(np.int64).sum()) / (float(k) * m),
+               'coverage': float(np.count_nonzero(min_rg <= kth_real)) / m,
+               'diversity_fake': float(np.sum(sum_fake)) / pairs,
+               'diversity_real': float(np.sum(sum_real)) / pairs}
+    out['n_coverage'] = m
+    return out
+
+
+class CoverageEvaluator:
+    """Precision / recall (Kynkaanniemi et al. 2019), density / coverage (Naeem et al. 2020) and
+    diversity over whole clips, per speaker and pooled (COVERAGE_METRICS): the
+    numbers that single out a generator which emits one plausible clip for every audio window.
+    a2m's own restatement, pinned in float64 by tests/coverage_ref.py:
+
+      feature   of a clip, float32 [D], in the generator's normalised space: 'pose' (D = T 2K) the
+                generated clip as it is and the real one (x - mean) / std as the loader's gather
+                normalises; 'motion' (D = (T - 1) 2K) their frame differences x[t] - x[t-1], in
+                which a static clip is the zero vector
+      d2(a,b)   max((|a|^2 + |b|^2) - 2 a.b, 0) in fp32 on the exact MFMA, within tol(a,b) =
+                4 D 2^-24 (|a|^2 + |b|^2) of the exact value; two identical clips are within tol
+                of 0, not necessarily at 0
+      R, G      the real and the generated clips of one speaker, or of every speaker ('all': the
+                pooled sets, no mean of the speakers' values); n = |R| = |G|
+      r_k2(x)   of x in a set S: the k-th smallest d2(x, y) over the y of S at another position
+                than x (a duplicate of x is a neighbour at distance about 0)
+      precision       #{g : some r has d2(g,r) <= r_k2(r)} / n
+      recall          #{r : some g has d2(r,g) <= r_k2(g)} / n
+      density         sum_g #{r : d2(g,r) <= r_k2(r)} / (k n)
+      coverage        #{r : min_g d2(r,g) <= r_k2(r)} / n
+      diversity_fake  the mean of sqrt(d2(g_j, g_j')) over the pairs j != j', each root and the sums
+                      in float64; diversity_real the same over R, the ceiling
+      n_coverage      n; a set with n <= k has NaN metrics
+
+    capacity: the most clips one pass holds (two [capacity, D] float32 buffers are allocated
+    here); T: frames a clip; 1 <= k <= 32.  block_rows: the rows of a distance slab (the
+    workspace is min(block_rows, n) x n floats, whatever n)."""
+
+    def __init__(self, pose_mean, pose_std, n_styles, capacity, T, k=5, feature='pose', device='cuda',
+                 block_rows=4096):
+        self.device = torch.device(device)
+        self.mean = torch.as_tensor(pose_mean).to(self.device, torch.float32).contiguous().reshape(-1)
+        self.std = torch.as_tensor(pose_std).to(self.device, torch.float32).contiguous().reshape(-1)
+        Fd = self.mean.numel()
+        if self.std.numel() != Fd or Fd % 4 or Fd < 4:
+            raise ValueError(f'pose_mean and pose_std must both hold a multiple of 4 values; got {Fd} and '
+                             f'{self.std.numel()}')
+        if feature not in F.COVERAGE_FEATURES:
+            raise ValueError(f'unknown feature {feature!r}: one of {tuple(F.COVERAGE_FEATURES)}')
+        if n_styles <= 0 or capacity <= 0 or block_rows <= 0 or not 1 <= k <= 32:
+            raise ValueError('n_styles, capacity and block_rows must be positive and 1 <= k <= 32')
+        if T <= F.COVERAGE_FEATURES[feature]:
+            raise ValueError(f"feature {feature!r} needs T > {F.COVERAGE_FEATURES[feature]}, got {T}")
+        self.n_styles, self.capacity, self.T, self.k = int(n_styles), int(capacity), int(T), int(k)
+        self.feature, self.Fd, self.block_rows = feature, Fd, int(block_rows)
+        self.D = (self.T - F.COVERAGE_FEATURES[feature]) * Fd
+        self.feat_fake = torch.zeros(self.capacity, self.D, device=self.device)
+        self.feat_real = torch.zeros(self.capacity, self.D, device=self.device)
+        self.styles = torch.full((self.capacity,), -1, dtype=torch.int32, device=self.device)
+        self.n = 0
+        # the per-row results of every set (the speakers partition the clips, 'all' holds them
+        # again) in one float64 arena, as PoseEvaluator's: result() reads them once
+        R = 2 * self.capacity
+        half = (R + 1) // 2
+        sizes = [('kth_real', half, torch.float32), ('kth_fake', half, torch.float32), ('min_rg', half, torch.float32),
+                 ('min_gr', half, torch.float32), ('cnt_prec', half, torch.int32), ('cnt_rec', half, torch.int32),
+                 ('sum_real', R, torch.float64), ('sum_fake', R, torch.float64)]
+        self._layout, n = [], 0
+        for name, words, dtype in sizes:
+            self._layout.append((name, n, words, dtype))
+            n += words
+        self._arena = torch.zeros(n, dtype=torch.float64, device=self.device)
+        self._rows = self._views(self._arena)
+        self._slab = None
+
+    def _views(self, arena):
+        return {name: arena[a:a + words].view(dtype) for name, a, words, dtype in self._layout}
+
+    def reset(self):
+        self.n = 0
+
+    def state(self):
+        """The pass so far as device tensors (views, not copies): feat_fake and feat_real [n, D], the
+        feature rows in the order of the update() calls, styles int32 [n], and n, the row count."""
+        n = self.n
+        return {'feat_fake': self.feat_fake[:n], 'feat_real': self.feat_real[:n], 'styles': self.styles[:n], 'n': n}
+
+    def update(self, fake_norm, real_px, style):
+        """Adds one batch: fake_norm [n, T, 2K] the generator's normalised output, real_px [n, T, 2K]
+        the neck-subtracted pose in pixels, style int32 [n] on the device (what
+        PoseEvaluator.update gets).  One launch, no host synchronisation, no allocation.  The row the
+        batch starts at is a host value (batch sizes are known on the host), so successive updates
+        are not one node of a HIP graph that could be replayed across batches.  ValueError, before
+        any launch, for a batch that does not fit into capacity."""
+        n, T, Fd = fake_norm.shape
+        if (T, Fd) != (self.T, self.Fd):
+            raise ValueError(f'clips of [{T}, {Fd}]; the evaluator was built for [{self.T}, {self.Fd}]')
+        if self.n + n > self.capacity:
+            raise ValueError(f'{self.n} + {n} clips exceed the capacity {self.capacity}')
+        if n == 0:
+            return
+        F.coverage_store(fake_norm, real_px, style, self.mean, self.std, self.n, self.feat_fake, self.feat_real,
+                         self.styles, self.feature)
+        self.n += n
+
+    def _slab_for(self, na, m):
+        if self._slab is None or self._slab.numel() < na * m:
+            self._slab = torch.empty(na * m, device=self.device)
+        return self._slab[:na * m].view(na, m)
+
+    def result(self, per_row=False):
+        """{style id: metrics, ..., 'all': metrics}; metrics holds COVERAGE_METRICS.  Reads the
+        styles, builds the row list of every speaker and of 'all' (the clips whose style is in
+        range) on the host, and per set runs R|R and G|G (the radii and the diversity sums), then
+        G|R (precision, density) and R|G (recall, coverage), a slab of at most block_rows rows at
+        a time; the per-row vectors are read back once.  per_row=True returns (that dict, {key:
+        per-row vectors}) for the sets with more than k clips: rows (positions in state()'s
+        buffers), kth_real and kth_fake (the radii r_k2), cnt_prec (per generated clip, the real
+        balls it lies in), cnt_rec (per real clip, the generated balls it lies in), min_rg (per
+        real clip, the distance to the nearest generated one), sum_real and sum_fake (the row
+        sums of sqrt d2): which clips are off the manifold, and which are not covered."""
+        S, k, n = self.n_styles, self.k, self.n
+        styles = self.styles[:n].cpu().numpy()
+        sets = [(s, np.flatnonzero(styles == s)) for s in range(S)]
+        sets.append(('all', np.flatnonzero((styles >= 0) & (styles < S))))
+        live = [(key, rows) for key, rows in sets if len(rows) > k]
+        spans, o = {}, 0
+        for key, rows in live:
+            spans[key] = (o, len(rows))
+            o += len(rows)
+        if live:
+            rows_dev = torch.from_numpy(np.concatenate([rows for _, rows in live]).astype(np.int32)).to(self.device)
+        v = self._rows
+        for key, _ in live:
+            o, m = spans[key]
+            rows = rows_dev[o:o + m]
+            blocks = [(a0, min(self.block_rows, m - a0)) for a0 in range(0, m, self.block_rows)]
+            for feat, kth, sums in ((self.feat_real, v['kth_real'], v['sum_real']),
+                                    (self.feat_fake, v['kth_fake'], v['sum_fake'])):
+                for a0, na in blocks:
+                    slab = F.pair_dist2(feat, rows[a0:a0 + na], feat, rows, True, a0, self._slab_for(na, m))
+                    F.row_kth(slab, k, True, kth[o + a0:o + a0 + na], sums[o + a0:o + a0 + na])
+            for fa, fb, r2, cnt, low in ((self.feat_fake, self.feat_real, v['kth_real'], v['cnt_prec'], v['min_gr']),
+                                         (self.feat_real, self.feat_fake, v['kth_fake'], v['cnt_rec'], v['min_rg'])):
+                for a0, na in blocks:
+                    slab = F.pair_dist2(fa, rows[a0:a0 + na], fb, rows, out=self._slab_for(na, m))
+                    F.row_cover(slab, r2[o:o + m], cnt[o + a0:o + a0 + na], low[o + a0:o + a0 + na])
+        host = {name: t.numpy() for name, t in self._views(self._arena.cpu()).items()} if live else {}
+        names = ('kth_real', 'cnt_prec', 'cnt_rec', 'min_rg', 'sum_real', 'sum_fake')
+        out = {}
+        for key, rows in sets:
+            if key in spans:
+                o, m = spans[key]
+                out[key] = _coverage_metrics(k, *(host[name][o:o + m] for name in names))
+            else:
+                out[key] = _coverage_metrics(k, *(np.zeros(len(rows)) for _ in names))
+        if not per_row:
+            return out
+        vectors = {}
+        for key, rows in live:
+            o, m = spans[key]
+            vectors[key] = dict({name: host[name][o:o + m].copy() for name in names + ('kth_fake',)}, rows=rows)
+        return out, vectors
+
+
 def evaluate(generator, loader, split='test', pose_mean=None, pose_std=None, audio_mean=None, audio_std=None,
-             sync=False, sync_kwargs=None, beat_sigma=1.0, **evaluator_kwargs):
+             sync=False, sync_kwargs=None, beat_sigma=1.0, coverage=False, coverage_kwargs=None,
+             **evaluator_kwargs):
     """One evaluation pass of `generator` over a split of a PatsLoader: result() of a PoseEvaluator,
     keyed by speaker name (loader.speaker_dict), 'all' and 'dropped'.  pose_mean, pose_std: the
     statistics the generator was trained with (its output is de-normalised with them);
@@ -339,12 +520,22 @@ def evaluate(generator, loader, split='test', pose_mean=None, pose_std=None, aud
     sync=True adds the SYNC_METRICS of an AudioSyncEvaluator(**sync_kwargs) to every speaker's entry
     and to 'all' (two more launches a batch and a second host read after the last batch); it gets
     the audio the generator got and the audio_std it was standardised with.  beat_sigma: see
-    AudioSyncEvaluator.result."""
+    AudioSyncEvaluator.result.
+    coverage=True adds the COVERAGE_METRICS of a CoverageEvaluator(**coverage_kwargs: k, feature,
+    block_rows), sized from the split's clip count in the loader's tables, to every speaker's entry
+    and to 'all': one more launch a batch, from the tensors PoseEvaluator.update gets, and the
+    distance passes of CoverageEvaluator.result() after the last batch.  Without it nothing of the
+    kind is constructed or launched."""
     if pose_mean is None or pose_std is None:
         raise ValueError('evaluate needs pose_mean and pose_std')
     ev = PoseEvaluator(pose_mean, pose_std, len(loader.speaker_dict), device=loader.device, **evaluator_kwargs)
     sev = AudioSyncEvaluator(len(loader.speaker_dict), audio_std=audio_std, device=loader.device,
                              **(sync_kwargs or {})) if sync else None
+    cev = None
+    if coverage:
+        pose = next(m for m in loader.modalities if m.startswith('pose'))
+        cev = CoverageEvaluator(pose_mean, pose_std, len(loader.speaker_dict), max(loader.index.size(split), 1),
+                                loader.index.geometry(pose)[2], device=loader.device, **(coverage_kwargs or {}))
     zero, one = torch.zeros_like(ev.mean), torch.ones_like(ev.std)
     flags = [(m, m.training) for m in generator.modules()]
     generator.eval()
@@ -352,15 +543,21 @@ def evaluate(generator, loader, split='test', pose_mean=None, pose_std=None, aud
         with torch.no_grad():
             for audio, real_px, style in loader.pairs(split, zero, one, audio_mean, audio_std, with_style=True):
                 fake = generator(audio)
-                ev.update(fake[0] if isinstance(fake, (tuple, list)) else fake, real_px, style)
+                fake = fake[0] if isinstance(fake, (tuple, list)) else fake
+                ev.update(fake, real_px, style)
                 if sev is not None:
                     sev.update(audio, ev.fake_px(*real_px.shape[:2]), real_px, style)
+                if cev is not None:
+                    cev.update(fake, real_px, style)
     finally:
         for m, flag in flags:
             m.training = flag
     res = ev.result()
     if sev is not None:
         for key, extra in sev.result(beat_sigma).items():
+            res[key].update(extra)
+    if cev is not None:
+        for key, extra in cev.result().items():
             res[key].update(extra)
     out = {name: res[i] for name, i in loader.speaker_dict.items()}
     out['all'], out['dropped'] = res['all'], res['dropped']

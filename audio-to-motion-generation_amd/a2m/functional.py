@@ -1374,6 +1374,111 @@ def window_median(arena, start, lo, n, window, interval, necksub=False):
     return out
 
 
+COVERAGE_FEATURES = {'pose': 0, 'motion': 1}
+
+
+def _check_rows(rows, name):
+    if not rows.is_cuda:
+        raise RuntimeError('a2m ops need device tensors (no CPU fallback); got a CPU tensor')
+    if rows.dtype != torch.int32 or rows.dim() != 1 or not rows.is_contiguous() or rows.numel() == 0:
+        raise ValueError(f'{name} must be a contiguous, non-empty int32 [n] tensor')
+
+
+def _check_slab(slab):
+    _check_dev(slab)
+    if slab.dim() != 2 or not slab.is_contiguous() or slab.numel() == 0:
+        raise ValueError(f'the slab must be a contiguous, non-empty [nA, nB] tensor, got {tuple(slab.shape)}')
+    return slab.shape
+
+
+def coverage_store(fake_norm, real_px, style, mean, std, row0, feat_fake, feat_real, styles, feature='pose'):
+    """One batch's clips as feature rows (a2m_coverage_store_f32): fake_norm, real_px [n, T, F],
+    style int32 [n]; rows row0 .. row0 + n of feat_fake and feat_real [capacity, D] and of styles
+    int32 [capacity] are written, D = T F for feature 'pose' (the generated clip as it is, the
+    real one normalised with mean / std [F] as the loader's gather normalises) and (T - 1) F for
+    'motion' (their frame differences).  One launch, no host synchronisation; row0 is a host
+    value.  ValueError where the rows do not fit."""
+    _check_dev(fake_norm, real_px, mean, std, feat_fake, feat_real)
+    if feature not in COVERAGE_FEATURES:
+        raise ValueError(f'coverage_store: unknown feature {feature!r}')
+    if fake_norm.dim() != 3 or fake_norm.shape != real_px.shape:
+        raise ValueError(f'coverage_store: fake_norm and real_px must both be [n, T, F]; got {tuple(fake_norm.shape)}, '
+                         f'{tuple(real_px.shape)}')
+    fake_norm, real_px, mean, std = fake_norm.contiguous(), real_px.contiguous(), mean.contiguous(), std.contiguous()
+    n, T, Fd = fake_norm.shape
+    D = (T - COVERAGE_FEATURES[feature]) * Fd
+    cap = feat_fake.shape[0]
+    if mean.numel() != Fd or std.numel() != Fd:
+        raise ValueError(f'coverage_store: mean and std must hold {Fd} values')
+    for t in (feat_fake, feat_real):
+        if t.dim() != 2 or not t.is_contiguous() or tuple(t.shape) != (cap, D):
+            raise ValueError(f'coverage_store: the feature buffers must be contiguous [{cap}, {D}]; got {tuple(t.shape)}')
+    _check_int(style, torch.int32, (n,), 'style')
+    _check_int(styles, torch.int32, (cap,), 'styles')
+    N.check(N.lib.a2m_coverage_store_f32(_p(fake_norm), _p(real_px), _p(style), _p(mean), _p(std), n, T, Fd,
+                                         COVERAGE_FEATURES[feature], int(row0), cap, _p(feat_fake), _p(feat_real),
+                                         _p(styles), _stream()), value_error=True)
+
+
+def pair_dist2(feat_a, rows_a, feat_b, rows_b, exclude_self=False, diag0=0, out=None):
+    """The slab d2 [nA, nB] of squared distances between rows rows_a of feat_a and rows rows_b of
+    feat_b ([cap, D] feature buffers, int32 row lists on the device; a2m_pair_dist2_f32):
+    max((|a|^2 + |b|^2) - 2 a.b, 0) on the exact fp32 MFMA, within 4 D 2^-24 (|a|^2 + |b|^2) of the
+    exact value.  exclude_self: element (i, diag0 + i) is +inf (rows_a is rows_b[diag0 : diag0 + nA]).
+    out: a contiguous [nA, nB] tensor to write.  No host synchronisation."""
+    _check_dev(feat_a, feat_b, out)
+    _check_rows(rows_a, 'rows_a')
+    _check_rows(rows_b, 'rows_b')
+    for t in (feat_a, feat_b):
+        if t.dim() != 2 or not t.is_contiguous() or t.shape[1] != feat_a.shape[1]:
+            raise ValueError('pair_dist2: the feature buffers must be contiguous [cap, D] with one D')
+    nA, nB = rows_a.numel(), rows_b.numel()
+    if out is None:
+        out = torch.empty(nA, nB, device=feat_a.device)
+    if tuple(out.shape) != (nA, nB) or not out.is_contiguous():
+        raise ValueError(f'pair_dist2: out must be a contiguous [{nA}, {nB}] tensor')
+    N.check(N.lib.a2m_pair_dist2_f32(_p(feat_a), feat_a.shape[0], _p(rows_a), nA, _p(feat_b), feat_b.shape[0],
+                                     _p(rows_b), nB, feat_a.shape[1], int(bool(exclude_self)), int(diag0), _p(out),
+                                     out.numel() * 4, _stream()), value_error=True)
+    return out
+
+
+def row_kth(slab, k, exclude_self=False, kth=None, sums=None):
+    """Per row of a slab [nA, nB] of values >= 0 or +inf (a2m_row_kth_f32): (kth float32 [nA], the
+    k-th smallest value, 1 <= k <= 32, exact, ties ordered by column; sums float64 [nA], the sum of
+    sqrt(double(v)) over the row's finite entries).  exclude_self: every row holds one +inf of its
+    own, so k must stay below nB.  kth and sums may be passed in.  No host synchronisation."""
+    nA, nB = _check_slab(slab)
+    if kth is None:
+        kth = torch.empty(nA, device=slab.device)
+    if sums is None:
+        sums = torch.empty(nA, dtype=torch.float64, device=slab.device)
+    _check_dev(kth)
+    assert kth.is_contiguous() and tuple(kth.shape) == (nA,)
+    _check_f64(sums, (nA,), 'sums')
+    N.check(N.lib.a2m_row_kth_f32(_p(slab), nA, nB, int(k), int(bool(exclude_self)), _p(kth), _p(sums), _stream()),
+            value_error=True)
+    return kth, sums
+
+
+def row_cover(slab, r2, count=None, rowmin=None):
+    """Per row of a slab [nA, nB] (a2m_row_cover_f32): (count int32 [nA], the number of columns j
+    with slab[row, j] <= r2[j]; rowmin float32 [nA], the row's smallest value).  r2 float32 [nB].
+    count and rowmin may be passed in.  No host synchronisation."""
+    nA, nB = _check_slab(slab)
+    _check_dev(r2, rowmin)
+    if r2.dim() != 1 or not r2.is_contiguous() or r2.numel() != nB:
+        raise ValueError(f'row_cover: r2 must be a contiguous [{nB}] tensor')
+    if count is None:
+        count = torch.empty(nA, dtype=torch.int32, device=slab.device)
+    if rowmin is None:
+        rowmin = torch.empty(nA, device=slab.device)
+    _check_int(count, torch.int32, (nA,), 'count')
+    assert rowmin.is_contiguous() and tuple(rowmin.shape) == (nA,)
+    N.check(N.lib.a2m_row_cover_f32(_p(slab), nA, nB, _p(r2), _p(count), _p(rowmin), _stream()), value_error=True)
+    return count, rowmin
+
+
 def clip_velocity(arena, start, lo, n, window, interval):
     """Mean 2-D speed of the non-neck joints, pixels per frame, of the clips at table positions
     [lo, lo + n) of start (a2m_clip_velocity_f32): arena [rows, C] in the loader's planar pose

@@ -995,6 +995,64 @@ int a2m_window_median_f32(const float* arena, const int64_t* start, int64_t lo, 
                           int32_t window, int32_t interval, int32_t mode, float* out, void* ws,
                           size_t ws_bytes, void* stream);
 
+/* ---- Sample-level set metrics of the test epoch (a2m.evaluation.CoverageEvaluator; csrc/coverage.hip) ----
+ * Precision / recall, density / coverage and diversity over whole clips from four
+ * kernels.  All take a stream, issue no host synchronisation, use no atomics and no workspace
+ * shared between workgroups, and give byte-identical results from run to run.  Inputs must be finite.
+ *
+ * a2m_coverage_store_f32: the feature rows of one batch.  fake_norm, real_px [n][T][Fd] float32,
+ * style int32[n], mean / std_ [Fd]; rows row0 .. row0 + n of feat_fake and feat_real [capacity][D]
+ * and of styles int32[capacity] are written.  A2M_COVERAGE_POSE (D = T*Fd): the generated clip as it
+ * is, the real clip (x - mean[c]) / (std[c] < 1e-7 ? 1 : std[c]), one rounding a step (the loader's
+ * gather formula).  A2M_COVERAGE_MOTION (D = (T-1)*Fd): x[t+1] - x[t] of those, one fp32
+ * subtraction each.  row0 is a host value: successive batches are not one replayable graph node.
+ * A2M_EINVAL ("coverage_store: ...") before any launch: a NULL pointer; an unknown feature; n <= 0;
+ * T < 1 (motion: T < 2); Fd <= 0 or Fd % 4; row0 < 0 or row0 + n > capacity; poses, statistics or
+ * feature buffers not 16-byte aligned; D > 2^30 or n*D >= 2^40.
+ *
+ * a2m_pair_dist2_f32: slab[i][j] (row-major [nA][nB] float32) =
+ *   max((|a_i|^2 + |b_j|^2) - 2 a_i.b_j, 0),  a_i = feat_a[rows_a[i]], b_j = feat_b[rows_b[j]]
+ * for device int32 row lists into feature buffers [cap][D]; a row number outside [0, cap) is read
+ * as the nearest valid row, so no list makes the kernel read outside the buffers.  a.b on the
+ * exact fp32 MFMA (v_mfma_f32_32x32x2_f32) as one k-ordered fma chain per element, the norms as
+ * fixed fma chains and a fixed 16-lane tree: the value is a function of the two vectors alone, and
+ * equal vectors give bitwise-equal distances wherever they sit.  Error: |d2 - exact| <=
+ * 4 D 2^-24 (|a|^2 + |b|^2); two identical vectors get a distance within that of 0, not
+ * necessarily 0.  exclude_self = 1 writes +inf at (i, diag0 + i): rows_a is then the sub-list of
+ * rows_b that starts at its position diag0.  The slab is the workspace: slab_bytes >=
+ * a2m_pair_dist2_ws_bytes(nA, nB) = 4 nA nB (0 for sizes the entry refuses).
+ * A2M_EINVAL ("pair_dist2: ...") before any launch: a NULL pointer; nA, nB, a capacity <= 0; D <= 0
+ * or D % 4; D > 2^30; nA > 65535 * 64; nB > 2^31 - 2^16; a capacity > 2^31 - 1; exclude_self not
+ * 0 / 1; diag0 < 0, diag0 != 0 without exclude_self, diag0 + nA > nB with it; misaligned feature
+ * buffers (16 bytes), row lists or slab (4); slab_bytes too small.
+ *
+ * a2m_row_kth_f32: per row of a slab [nA][nB] whose values are >= +0 or +inf, kth[row] = the k-th
+ * smallest value (1 <= k <= 32), exact, ties ordered by column (selection on the 64-bit key
+ * bits << 32 | column), and sums[row] (float64) = the sum of sqrt((double) v) over the row's finite
+ * entries: every lane of the row's wave adds its columns lane, lane + 64, ... in ascending order,
+ * then a butterfly over the lanes.  exclude_self = 1 says that every row holds one +inf of its own.
+ * A2M_EINVAL ("row_kth: ...") before any launch: a NULL pointer; nA or nB <= 0 or > 2^31 - 2^16;
+ * k outside 1..32; exclude_self not 0 / 1; k > nB - exclude_self; misaligned pointers.
+ *
+ * a2m_row_cover_f32: per row of such a slab, count[row] (int32) = #{j : slab[row][j] <= r2[j]} and
+ * rowmin[row] = the row's smallest value.
+ * A2M_EINVAL ("row_cover: ...") before any launch: a NULL pointer; nA or nB <= 0 or > 2^31 - 2^16;
+ * misaligned pointers. */
+#define A2M_COVERAGE_POSE 0
+#define A2M_COVERAGE_MOTION 1
+int a2m_coverage_store_f32(const float* fake_norm, const float* real_px, const int32_t* style,
+                           const float* mean, const float* std_, int32_t n, int32_t T, int32_t Fd,
+                           int32_t feature, int64_t row0, int64_t capacity, float* feat_fake,
+                           float* feat_real, int32_t* styles, void* stream);
+size_t a2m_pair_dist2_ws_bytes(int64_t nA, int64_t nB);
+int a2m_pair_dist2_f32(const float* feat_a, int64_t cap_a, const int32_t* rows_a, int64_t nA,
+                       const float* feat_b, int64_t cap_b, const int32_t* rows_b, int64_t nB, int64_t D,
+                       int32_t exclude_self, int64_t diag0, float* slab, size_t slab_bytes, void* stream);
+int a2m_row_kth_f32(const float* slab, int64_t nA, int64_t nB, int32_t k, int32_t exclude_self, float* kth,
+                    double* sums, void* stream);
+int a2m_row_cover_f32(const float* slab, int64_t nA, int64_t nB, const float* r2, int32_t* count,
+                      float* rowmin, void* stream);
+
 /* ---- Train samplers over the loader's arena (a2m/sampling.py; csrc/sampling.hip) ----
  * The device half of PatsLoader.train_sampler: the mean joint speed of every clip of a split, exact
  * order statistics of those speeds, and the binning of the clips.  All three take a stream, issue no
